@@ -13,11 +13,14 @@ iteration is one DDPSolver::procOnce (DDPSolver.hpp:143-340: linearise + regular
 forward pass); instances that meet the reference's termination tests earlier stop earlier, and only iterations that
 were actually executed are counted (sum of traceDataList().back().iter over the batch / 4096).  Inputs are already
 resident in HBM.  value = n_gpus * K * (executed instance-iterations per solve / 4096) / t, t = max over ranks of the
-wall time between two barrier + device-synchronise brackets.  Weak scaling: every rank owns its own 4096 instances; the
-only collective is ONE all_gather of the packed results (X | U | cost | status | iters per shard; RCCL over xGMI) at the end of
-the timed job.  --global-batch G cuts ONE batch of G instances into contiguous balanced shards instead (strong split, uneven
-shards padded to one fixed-size all-gather), --verify-gather compares the gathered records with the unsharded solve.
-The CPU baseline leg runs first, the GPU legs last; the number of timed blocks is fixed before the timed region.
+wall time of the K steps (from a barrier + device-synchronise bracket to the stream synchronise after the last step).  Weak
+scaling: every rank owns its own 4096 instances; the only collective is ONE all_gather of the packed results (X | U | cost |
+status | iters per shard; RCCL over xGMI) after the timed steps, reported as config.final_gather_ms.  --global-batch G cuts
+ONE batch of G instances into contiguous balanced shards instead (strong split, uneven shards padded to one fixed-size
+all-gather), --verify-gather compares the gathered records with the unsharded solve.
+The CPU baseline leg runs first, the GPU legs last; the timed job is exactly --steps steps after --warmup untimed ones, and
+ms_per_step is its wall time / --steps.  --dump-outputs DIR writes what the last timed step returned (X, U, cost, status, iters;
+the FMPC workload: its variable, status, iters) as DIR/<name>.npy, for comparing two builds on the same inputs.
 
 After the timed job the default (c2, nominal) run also measures SURVEY.md 8(d)'s two timing modes with the same handle —
 m1 (termination tests disabled, N = 50 iterations forced) and m2 (solve to convergence, max_iter 500) — and reports them as
@@ -53,9 +56,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# streams share GPU_MAX_HW_QUEUES hardware queues (default 4): the pooled legs (m2_overlapped, c3's pooled) overlap as many batches as
-# there are queues.  Read when the HIP runtime initialises, i.e. before torch touches the device (nmpc_amd/csrc/capi.hip).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 LANE_MAPPINGS = {
@@ -105,7 +105,7 @@ def parse_args():
     ap.add_argument("--share-devices", action="store_true",
                     help="allow more ranks than visible devices (rank r on device r %% n_devices, the final gather over gloo because RCCL "
                          "wants one device per rank): the one-GPU test box.  Without it a job with fewer devices than ranks is refused")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (one batched solve each); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["fmpc"], default="c2",
                     help="c2 (default) is BASELINE.json's metric configuration; c3 / c4 / c5 are the other configs "
@@ -122,10 +122,8 @@ def parse_args():
                     help="override Configuration::cost_update_thre.  c4 (fp32) defaults to 1e-3: the reference's 1e-7 is below the "
                          "resolution of an fp32 cost, where the accept test is rounding noise in the fp32 ORACLE itself (DESIGN.md "
                          "3a); the rate with the reference's default rides along as config.default_threshold_value")
-    ap.add_argument("--min-seconds", type=float, default=3.0,
-                    help="the timed job lasts about this long: blocks of --steps steps are repeated (value is taken over all of "
-                         "them; the number of blocks is fixed BEFORE the timed region from an untimed calibration block, so the timed "
-                         "region holds no collective; config.block_ms_per_step_{min,median,max} are the per-block step times)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="no effect: the timed job is exactly --steps steps (accepted so that older command lines still parse)")
     ap.add_argument("--no-extra-modes", action="store_true", help="skip the m1 / m2 (c2) and fp32-tolerance (c4) extra legs")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary legs of the default line (c3, c4, c4f64, c5, fmpc, centroidal: >= --secondary-seconds each, "
@@ -135,6 +133,10 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=6.0,
                     help="sizing target of the CPU baseline sample (the sustained all-core rate is ~3x below the probe: ~20 s)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed job, write what its last step returned to the caller as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed sample of instances beyond that, their indices in instances.npy).  The inputs "
+                         "depend on the arguments only, so two builds can be compared output for output")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong split: ONE batch of this many instances (the workload's generator, --seed) cut into contiguous, "
                          "balanced shards over the ranks (nmpc_amd.sharding.shard_range: sizes differ by at most one) instead of "
@@ -382,9 +384,36 @@ def secondary_legs(device_index: int, seed: int, iters_per_solve: int, min_secon
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: write each array as <out_dir>/<name>.npy, float32 / float64 as they are and integer fields as float64.  The arrays
+    share a leading instance axis; when they come to more than 64 MB together, the same fixed sample of instances (seed 0, sorted) is
+    taken from every one and its indices go to instances.npy."""
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    n_inst = next(iter(arrs.values())).shape[0]
+    assert all(a.shape[0] == n_inst for a in arrs.values()), {k: a.shape for k, a in arrs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        per_inst = total / n_inst + 8  # (+ its index)
+        keep = int((DUMP_MAX_BYTES - 128 * 1024) // per_inst)  # (room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n_inst, size=keep, replace=False))
+        arrs = {name: a[idx] for name, a in arrs.items()}
+        arrs["instances"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def launch_ranks(n: int) -> None:
     """`python bench.py --gpus N` outside a launcher: become the launcher of N ranks of this very command line (one process per GPU,
-    rendezvous on 127.0.0.1, a free port) — the form the driver itself uses for N > 1.  Does not return."""
+    rendezvous on 127.0.0.1, a free port) — the form the driver itself uses for N > 1.  Runs them as a child process and exits with
+    its status: does not return."""
+    import subprocess
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -395,7 +424,9 @@ def launch_ranks(n: int) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    # a launcher killed by signal s has returncode -s: exit with 128 + s, the status a shell reports for it (134 abort, 139 fault)
+    sys.exit(128 - rc if rc < 0 else rc)
 
 
 def check_world(args, world: int, n_dev: int) -> None:
@@ -410,6 +441,8 @@ def check_world(args, world: int, n_dev: int) -> None:
 
 def main():
     args = parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args.gpus)
     if args.workload == "fmpc":  # the FMPC path has its own script behind the same contract
@@ -518,36 +551,16 @@ def main():
         step()
     solver.synchronize()
     solver.timingStats(reset=True)
-
-    # How many blocks of --steps steps the timed job holds is settled BEFORE it starts — one untimed calibration block, the
-    # slowest rank's time decides — so that the timed region contains no collective and no host round trip besides the
-    # per-block stream synchronise.
     red_dev = dev if backend == "nccl" else torch.device("cpu")
+
+    # The timed job: exactly --steps steps, from a barrier + device synchronise to the stream synchronise after the last one; no
+    # collective and no host round trip inside it.
     barrier()
-    t_cal = time.perf_counter()
+    t_begin = time.perf_counter()
     for _ in range(args.steps):
         step()
     solver.synchronize()
-    cal = torch.tensor([time.perf_counter() - t_cal], dtype=torch.float64, device=red_dev)
-    if world > 1:
-        dist.all_reduce(cal, op=dist.ReduceOp.MAX)
-    n_blocks = int(min(10000, max(2, np.ceil(args.min_seconds / max(float(cal[0]), 1e-6)))))
-    solver.timingStats(reset=True)
-
-    # The timed job: n_blocks blocks of exactly --steps steps between two barrier + device-synchronise brackets.
-    barrier()
-    t_begin = time.perf_counter()
-    block_s = []
-    t_prev = t_begin
-    for _ in range(n_blocks):
-        for _ in range(args.steps):
-            step()
-        solver.synchronize()
-        t_now = time.perf_counter()
-        block_s.append(t_now - t_prev)
-        t_prev = t_now
-    first_block_s = block_s[0]
-    total_steps = n_blocks * args.steps
+    total_steps = args.steps
     t_solve = time.perf_counter()
     # the one collective of the job: gather the packed results of every shard
     off = 0
@@ -561,14 +574,17 @@ def main():
         dist.all_gather_into_tensor(d_all, d_res if backend == "nccl" else d_res.cpu())
     barrier()
     t_end = time.perf_counter()
+    if args.dump_outputs:  # what the caller of the timed path receives from its last step (before the extra legs reuse the handle)
+        dumped = {"X": solver.X(), "U": solver.U(), "cost": solver.cost(), "status": solver.status(), "iters": solver.iters()}
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), dumped)
 
-    mine = torch.tensor([t_end - t_begin, t_end - t_solve, t_solve - t_begin, first_block_s], dtype=torch.float64, device=red_dev)
+    mine = torch.tensor([t_end - t_begin, t_end - t_solve, t_solve - t_begin], dtype=torch.float64, device=red_dev)
     per_rank = [mine.clone() for _ in range(world)]
     elapsed_t = mine.clone()
     if world > 1:
         dist.all_gather(per_rank, mine)
         dist.all_reduce(elapsed_t, op=dist.ReduceOp.MAX)
-    elapsed, gather_s, first_block = float(elapsed_t[0]), float(elapsed_t[1]), float(elapsed_t[3])
+    elapsed, gather_s = float(elapsed_t[2]), float(elapsed_t[1])  # (the timed steps; the gather after them is reported on its own)
 
     n_solves, total_ms, kernel_ms = solver.timingStats()
     tr = solver.trace()  # (B, max_iter+1, 12) of the last solve; rows beyond an instance's last iteration are zero
@@ -776,14 +792,7 @@ def main():
             "iterations_per_step": args.iters_per_solve if args.mode != "m2" else 500,
             "solves_per_s": (args.global_batch if args.global_batch > 0 else world * wl.B) * total_steps / elapsed,
             "timed_steps_total": total_steps,
-            "timed_blocks": n_blocks,
             "timed_seconds": elapsed,
-            "first_block_ms_per_step": 1e3 * first_block / args.steps,
-            "block_ms_per_step_min": 1e3 * float(np.min(block_s)) / args.steps,
-            "block_ms_per_step_median": 1e3 * float(np.median(block_s)) / args.steps,
-            "block_ms_per_step_max": 1e3 * float(np.max(block_s)) / args.steps,
-            "value_at_fastest_block": (job_it_per_solve / wl.B) / (float(np.min(block_s)) / args.steps) if world == 1 else None,
-            "value_at_median_block": (job_it_per_solve / wl.B) / (float(np.median(block_s)) / args.steps) if world == 1 else None,
             "gathered_record": "per shard, field-major: X | U | cost | status, iters (int32)",
             "iteration_histogram": hist,
             "instance_iterations_per_step": job_it_per_solve,

@@ -259,6 +259,9 @@ def main(args, host_cores):
     elapsed_local = time.perf_counter() - t_begin
     iters = solver.iters()
     status = solver.status()
+    if args.dump_outputs:  # what the caller of the timed path receives from its last step
+        dumped = dict(zip(("x", "u", "lambda", "s", "nu"), solver.variable().arrays()), status=status, iters=iters)
+        bench.dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), dumped)
     inst_it = float(iters.sum())
 
     # one gather of the final variables of every shard (outside the per-step data path)

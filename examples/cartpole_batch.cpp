@@ -2,7 +2,7 @@
 // pattern of the reference's TestDDPCartPole (nmpc_ddp/tests/src/TestDDPCartPole.cpp:266-306, 388-403) with a
 // batch axis.  Build + run:
 //   g++ -std=c++17 -O2 -Iinclude examples/cartpole_batch.cpp -Lnmpc_amd/lib -lnmpc_hip_ddp
-//       -Wl,-rpath,$PWD/nmpc_amd/lib -o /tmp/cartpole_batch && /tmp/cartpole_batch
+//       -Wl,-rpath,$PWD/nmpc_amd/lib -o /tmp/cartpole_batch && /tmp/cartpole_batch [batch] [trace file]
 #include <cmath>
 #include <cstdio>
 #include <memory>
@@ -15,6 +15,7 @@ int main(int argc, char ** argv)
   using Problem = nmpc_amd::DDPProblemCartPole;
   using Solver = nmpc_amd::DDPSolverBatch<Problem>;
   const int batch = argc > 1 ? std::atoi(argv[1]) : 8;
+  const char * trace_path = argc > 2 ? argv[2] : "/tmp/CartPoleBatchTraceData.txt"; // (the reference test's file by default)
 
   // Instantiate problem (parameters can be edited exactly as in the reference test, :274-289)
   auto ddp_problem = std::make_shared<Problem>(0.01);
@@ -53,7 +54,7 @@ int main(int argc, char ** argv)
     std::printf("instance %d converged %d iter %d cost %.12e u0 %.12e theta_end %.6e\n", b, static_cast<int>(ok[b]),
                 trace.back().iter, cost, cd.u_list[0][0], cd.x_list.back()[1]);
   }
-  ddp_solver->dumpTraceDataList(0, "/tmp/CartPoleBatchTraceData.txt");
+  ddp_solver->dumpTraceDataList(0, trace_path);
   std::printf("solve %.3f ms (kernel %.3f ms)\n", ddp_solver->computationDuration().solve,
               ddp_solver->computationDuration().opt);
 

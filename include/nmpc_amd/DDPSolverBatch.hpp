@@ -907,10 +907,10 @@ public:
     {
       throw std::invalid_argument("n_handles should be positive");
     }
-    // one hardware queue per handle, or the streams that share one do not overlap (nmpc_hip_ddp_request_hw_queues: effective
-    // only before the first HIP call of the process — construct the pool first, or export GPU_MAX_HW_QUEUES)
+    // one hardware queue per handle, or the streams that share one do not overlap (nmpc_hip_ddp_request_hw_queues only reports
+    // whether the runtime has them: the queue count is the host's setting, GPU_MAX_HW_QUEUES)
     int took_effect = 0;
-    nmpc_hip_ddp_request_hw_queues(std::min(std::max(n_handles, 4), 64), &took_effect);
+    nmpc_hip_ddp_request_hw_queues(std::min(n_handles, 64), &took_effect);
     hw_queues_ok_ = took_effect != 0;
     for(int k = 0; k < n_handles; k++)
     {
@@ -918,8 +918,8 @@ public:
     }
   }
 
-  /** \brief Whether the HIP runtime has (or will have) one hardware queue per handle; false: it was already initialised with
-      fewer, and fewer batches overlap than the pool has handles. */
+  /** \brief Whether the HIP runtime has (or will have) one hardware queue per handle; false: fewer batches overlap than the pool
+      has handles. */
   inline bool hwQueuesOk() const
   {
     return hw_queues_ok_;

@@ -589,11 +589,10 @@ class DDPSolverBatch:
                         f"{t.duration_derivative:g} {t.duration_backward:g} {t.duration_forward:g}\n")
 
 
-def request_hw_queues(n: int = 16) -> bool:
-    """Ask the HIP runtime for at least n hardware queues (nmpc_hip_ddp_request_hw_queues: GPU_MAX_HW_QUEUES, read when the runtime
-    initialises; streams that share a queue do not overlap).  True when the request can still take effect or the runtime already
-    has that many; False when the runtime of this process is up with fewer — call it (or construct the pool) before anything touches
-    the device, or export GPU_MAX_HW_QUEUES yourself.  Importing nmpc_amd does not change the environment."""
+def request_hw_queues(n: int) -> bool:
+    """Whether the HIP runtime has (or will have) at least n hardware queues (nmpc_hip_ddp_request_hw_queues: GPU_MAX_HW_QUEUES, read
+    when the runtime initialises, default 4; streams that share a queue do not overlap).  Only reports: the queue count is the host's
+    setting, and nmpc_amd never changes GPU_MAX_HW_QUEUES."""
     ok = C.c_int(0)
     _capi.check(_capi.load().nmpc_hip_ddp_request_hw_queues(int(n), C.byref(ok)))
     return bool(ok.value)
@@ -610,12 +609,7 @@ class DDPSolverPool:
         if n_handles < 1:
             raise ValueError("n_handles should be positive")
         #: whether the runtime has (or will have) one hardware queue per handle; False: fewer batches overlap than there are handles
-        self.hw_queues_ok = request_hw_queues(min(max(n_handles, 4), 64))
-        if not self.hw_queues_ok:
-            import warnings
-            warnings.warn("DDPSolverPool: the HIP runtime is already initialised with GPU_MAX_HW_QUEUES=%s (< %d handles): streams that "
-                          "share a hardware queue do not overlap; call nmpc_amd.request_hw_queues() or export the variable before the first "
-                          "HIP call of the process" % (__import__("os").environ.get("GPU_MAX_HW_QUEUES", "unset (4)"), n_handles))
+        self.hw_queues_ok = request_hw_queues(min(n_handles, 64))
         self.solvers = [DDPSolverBatch(problem, batch_size, device=device) for _ in range(n_handles)]
         for s in self.solvers:
             # Configuration::ragged_schedule 0 (automatic) is off for a lone handle's solve() / solveDevice() — max_iter is only a cap,

@@ -1,7 +1,6 @@
 """C3 (bipedal, n = 2, m = 1, T = 300, 1024 instances): the kernel families the shape can run on, single batch and pooled
 (the A/B that was missing).   python scripts/c3_kernel_ab.py [B] [max_iter]"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np, torch  # noqa: E402
 import nmpc_amd  # noqa: E402

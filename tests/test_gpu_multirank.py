@@ -59,7 +59,7 @@ def test_bench_under_two_ranks():
     """bench.py launched the way the driver launches it for N > 1 (both ranks share device 0 here): one JSON line from rank 0,
     n_gpus = 2, the whole-job value is the sum of both ranks' work, per-rank solve and gather times are reported."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-devices", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
-                   "--no-extra-modes", "--min-seconds", "0.5"], 29643)
+                   "--no-extra-modes"], 29643)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -79,8 +79,7 @@ def test_plain_python_bench_gpus_2_launches_two_ranks():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-extra-modes", "--cpu-seconds", "0.5",
-            "--min-seconds", "0.5"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-extra-modes", "--cpu-seconds", "0.5"]
     r = subprocess.run(base + ["--share-devices"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -96,7 +95,7 @@ def test_plain_python_bench_gpus_2_launches_two_ranks():
         assert r.returncode != 0 and "visible device" in (r.stdout + r.stderr) and not [l for l in r.stdout.splitlines() if l.startswith("{")]
     # a launcher that started another number of ranks than --gpus says is refused as well
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-devices", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                   "--no-extra-modes", "--min-seconds", "0.2"], 29651)
+                   "--no-extra-modes"], 29651)
     assert r.returncode != 0 and "--gpus 4" in (r.stdout + r.stderr)
 
 
@@ -105,7 +104,7 @@ def test_bench_c5_uneven_strong_split_gathers_the_unsharded_solve():
     fixed-size all-gather): the gathered records — X | U | cost | status | iters of every shard — equal the unsharded solve of
     the same batch bit for bit (both sides on the fp64 tile kernel), and the line says so."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--workload", "c5", "--gpus", "2", "--share-devices", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                   "--no-extra-modes", "--min-seconds", "0.2", "--global-batch", "8201", "--verify-gather"], 29645)
+                   "--no-extra-modes", "--global-batch", "8201", "--verify-gather"], 29645)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -123,7 +122,7 @@ def test_bench_c4_fp32_two_ranks_at_global_batch_8192_equal_the_unsharded_solve(
     tile kernel's float instantiation — families that differ in the last bits.  The shards set the whole batch's size as their dispatch
     batch (bench.py --global-batch; nmpc_hip_ddp_set_dispatch_batch) and return the unsharded solve bit for bit."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--workload", "c4", "--gpus", "2", "--share-devices", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                   "--no-extra-modes", "--min-seconds", "0.2", "--global-batch", "8192", "--cost-update-thre", "1e-7", "--verify-gather"], 29649)
+                   "--no-extra-modes", "--global-batch", "8192", "--cost-update-thre", "1e-7", "--verify-gather"], 29649)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["config"]["shard_sizes"] == [4096, 4096] and d["config"]["gather_verified"] is True and d["dtype"] == "f32"

