@@ -36,10 +36,7 @@
 // (mpc_kernels.hpp) advances the handle's float arrays in place.
 #pragma once
 
-#include <atomic>
-
 #include <cstring>
-#include <new>
 #include <type_traits>
 
 #include <nmpc_amd/hip/model_ops.hpp>
@@ -1699,319 +1696,8 @@ __global__ __launch_bounds__(kTileThreads) void ddp_solve_tile32_kernel(const Pr
   TileSolver32<Problem, kOwnProblem, kConstrained> solver(problem, cfg, buf, lds_tile32);
   solver.solve();
 }
-
-/** Type-erased operations (model_ops.hpp) of an fp32 problem type served by the tile kernel. */
-template<class Problem>
-struct ModelOpsTile32
-{
-  using Solver = TileSolver32<Problem, false, false>;
-  static void defaultParams(void * out)
-  {
-    new(out) Problem();
-  }
-  /** Round 4: the fp64 tile kernel has a float instantiation (ddp_kernels_tile64.hpp: the same kernel with v_mfma_f32_16x16x4 and
-      the lanes of a row holding the tile's columns in the order that makes the f32 instruction's result layout the f64 one).  It
-      is the fp32 kernel of the shapes THIS file's kernel does not take (m > 4, n not in {4, 8, 12}: ModelOpsTile64Float below).
-      On the shapes both take (unconstrained solves of 5 <= n <= 12; BoxQP in float is this file's only) the choice is per launch,
-      measured on the quadrotor (profiles/r04_c4_dispatch_sweep.txt, scripts/c4_dispatch_sweep*.py):
-        * this file's kernel is the leaner one per full sweep (16 MFMAs + 125 other instructions a step against 10 + 250), but a
-          workgroup is 32 instances whatever the batch, its model wave linearises all 32 lanes of every timestep and its matrix
-          waves step all their slots — a sweep costs the same however few instances still iterate, and batches below 8192 leave
-          CUs idle (64 .. 4096 instances: 0.77 - 0.86 ms per 2 iterations);
-        * the other kernel sizes its groups to the batch and deals a sweep's work by ACTIVE index: 1.3 - 2.6 x faster up to 4096
-          instances at any iteration count and threshold; on full chips (8192, 16384 instances) level for one to four iterations
-          and ahead from there (c4, max_iter 8: 1.95 k against 1.46 k it/s — the iteration counts of a batch are ragged, the late
-          sweeps nearly empty) AS LONG AS most line searches end at the first or second step size (its search is passes over the
-          horizon: the first two step sizes in one, the later ones in a second, the taken one in a third; this file's rolls every
-          step size out at once).  They do not once an fp32 solve iterates below the resolution of a float cost: 0.7 - 0.9 x at
-          cost_update_thre = 1e-4 and below (the reference's default 1e-7: 0.6 x), level at 3e-4, 1.0 - 1.3 x at 1e-3.
-      Hence: the float instantiation below 8192 instances; on full chips with cost_update_thre >= 5e-4.
-      NMPC_HIP_DDP_KERNEL=tile32 / tile64 forces one of them (A/B measurements; tests/test_gpu_fp32.py runs on both). */
-  static constexpr bool kTile64Float = Problem::kStateDim >= 5 && Problem::kStateDim <= 15 && Problem::kInputDimMax >= 1
-                                       && Problem::kInputDimMax <= 8 && !Problem::kDynamicInput;
-  //! batches that fill the chip with this kernel's fixed 32-instance workgroups: 32 x the number of CUs (8192 on MI355X)
-  static int fullChipBatch()
-  {
-    static int n_cu = 0; // of the current device at first use (the handles of one process sit on like devices)
-    if(n_cu == 0)
-    {
-      int device = 0;
-      if(hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess
-         || n_cu <= 0)
-      {
-        n_cu = 256;
-      }
-    }
-    return 32 * n_cu;
-  }
-  static constexpr double kTile64FloatFromThreshold = 5e-4;
-  static bool useTile64Float(int batch, const nmpc_hip_ddp_config & cfg)
-  {
-    if(!kTile64Float || cfg.with_input_constraint != 0)
-    {
-      return false;
-    }
-    const LaunchKnobs knobs = launchKnobs();
-    if(knobs.kernelIs("tile64"))
-    {
-      return true;
-    }
-    if(knobs.kernelIs("tile32"))
-    {
-      return false;
-    }
-    // (a shard of a larger solve takes the family the WHOLE batch would get: the two fp32 kernels differ in the last bits)
-    return knobs.batchFor(batch) < fullChipBatch() || cfg.cost_update_thre >= kTile64FloatFromThreshold;
-  }
-  static const char * kernelName(int batch, const nmpc_hip_ddp_config & cfg)
-  {
-    return useTile64Float(batch, cfg) ? "ddp_solve_tile64_kernel" : "ddp_solve_tile32_kernel";
-  }
-  /** The handle allocates every Scalar array with sizeof(Problem::Scalar) = 4 (ModelOps::scalar_bytes): same pointers, float view. */
-  static DeviceBuffersT<float> floatView(const DeviceBuffers & buf64)
-  {
-    DeviceBuffersT<float> buf;
-    buf.B = buf64.B;
-    buf.Bp = buf64.Bp;
-    buf.T = buf64.T;
-    buf.trace_rows = buf64.trace_rows;
-    buf.t0 = reinterpret_cast<const float *>(buf64.t0);
-    buf.x0 = reinterpret_cast<const float *>(buf64.x0);
-    buf.X = reinterpret_cast<float *>(buf64.X);
-    buf.U = reinterpret_cast<float *>(buf64.U);
-    buf.cost = reinterpret_cast<float *>(buf64.cost);
-    buf.kff = reinterpret_cast<float *>(buf64.kff);
-    buf.Kfb = reinterpret_cast<float *>(buf64.Kfb);
-    buf.trace = reinterpret_cast<float *>(buf64.trace);
-    buf.trace_last = reinterpret_cast<float *>(buf64.trace_last);
-    buf.dV = reinterpret_cast<float *>(buf64.dV);
-    buf.status = buf64.status;
-    buf.iters = buf64.iters;
-    buf.sel = buf64.sel;
-    buf.qp_ret = buf64.qp_ret;
-    buf.qp_free = buf64.qp_free;
-    buf.input_dim = buf64.input_dim;
-    buf.wpi_ws = reinterpret_cast<float *>(buf64.wpi_ws);
-    buf.phase_ticks = buf64.phase_ticks;
-    buf.params_batch = buf64.params_batch;
-    buf.lim_batch = buf64.lim_batch; // (the limits are read by the receding-horizon driver's clamp: doubles in every handle)
-    buf.lim_steps = buf64.lim_steps;
-    buf.lim_steps_per_instance = buf64.lim_steps_per_instance;
-    buf.lim_mm = buf64.lim_mm;
-    buf.lim_rows = buf64.lim_rows;
-    buf.lim_offset = buf64.lim_offset;
-    for(int i = 0; i < kMaxInputDim; i++)
-    {
-      buf.lim_lo[i] = buf64.lim_lo[i];
-      buf.lim_hi[i] = buf64.lim_hi[i];
-    }
-    return buf;
-  }
-  static hipError_t launchSolve(const void * params, const nmpc_hip_ddp_config & cfg, const DeviceBuffers & buf64,
-                                hipStream_t stream)
-  {
-    if(buf64.wpi_ws == nullptr)
-    {
-      return hipErrorNotSupported;
-    }
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    const DeviceBuffersT<float> buf = floatView(buf64);
-    if constexpr(kTile64Float)
-    {
-      if(useTile64Float(buf64.B, cfg))
-      {
-        if(buf.params_batch != nullptr)
-        {
-          return launchTile64<Problem, false, true>(problem, cfg, buf, stream);
-        }
-        return launchTile64<Problem, false, false>(problem, cfg, buf, stream);
-      }
-    }
-    constexpr size_t lds_bytes = Solver::kLdsBytes;
-    static std::atomic<bool> requested[64] = {}; // (several host threads may launch at once; the setup is idempotent)
-    int dev = 0;
-    if(hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-    {
-      return hipErrorInvalidDevice;
-    }
-    if(!requested[dev].load(std::memory_order_acquire))
-    {
-      for(const void * kernel : {reinterpret_cast<const void *>(&ddp_solve_tile32_kernel<Problem, false, false>),
-                                 reinterpret_cast<const void *>(&ddp_solve_tile32_kernel<Problem, true, false>),
-                                 reinterpret_cast<const void *>(&ddp_solve_tile32_kernel<Problem, false, true>),
-                                 reinterpret_cast<const void *>(&ddp_solve_tile32_kernel<Problem, true, true>)})
-      {
-        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes));
-        if(e != hipSuccess)
-        {
-          return e;
-        }
-      }
-      requested[dev].store(true, std::memory_order_release);
-    }
-    const dim3 g((buf.B + kTileInstances - 1) / kTileInstances), blk(kTileThreads);
-    const bool own = buf.params_batch != nullptr, box = cfg.with_input_constraint != 0;
-    if(own && box)
-    {
-      hipLaunchKernelGGL((ddp_solve_tile32_kernel<Problem, true, true>), g, blk, lds_bytes, stream, problem, cfg, buf);
-    }
-    else if(own)
-    {
-      hipLaunchKernelGGL((ddp_solve_tile32_kernel<Problem, true, false>), g, blk, lds_bytes, stream, problem, cfg, buf);
-    }
-    else if(box)
-    {
-      hipLaunchKernelGGL((ddp_solve_tile32_kernel<Problem, false, true>), g, blk, lds_bytes, stream, problem, cfg, buf);
-    }
-    else
-    {
-      hipLaunchKernelGGL((ddp_solve_tile32_kernel<Problem, false, false>), g, blk, lds_bytes, stream, problem, cfg, buf);
-    }
-    return hipGetLastError();
-  }
-  /** The receding-horizon driver's advance step (mpc_kernels.hpp) on the handle's float arrays. */
-  static hipError_t launchMpcAdvance(const void * params, const DeviceBuffers & buf64, const MpcAdvanceArgs & args, hipStream_t stream)
-  {
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    const DeviceBuffersT<float> buf = floatView(buf64);
-    hipLaunchKernelGGL((mpc_advance_kernel<Problem, float>), dim3(buf.Bp / kLanesPerBlock), dim3(kLanesPerBlock), 0, stream, problem,
-                       buf, args);
-    return hipGetLastError();
-  }
-  static void inputDims(const void *, double, int T, int * out)
-  {
-    for(int i = 0; i < T; i++)
-    {
-      out[i] = Problem::kInputDimMax;
-    }
-  }
-  static double dt(const void * params)
-  {
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    return static_cast<double>(problem.dt());
-  }
-  static size_t workspaceElems(int T)
-  {
-    size_t n = Solver::workspaceElems(T);
-    if constexpr(kTile64Float)
-    {
-      const size_t n64 = TileSolver64<Problem>::workspaceDoubles(T); // (elements of float: gain records + candidate trajectories)
-      n = n64 > n ? n64 : n;
-    }
-    return n;
-  }
-  static ModelOps make()
-  {
-    static_assert(std::is_trivially_copyable<Problem>::value, "a DDP problem must be trivially copyable: it is passed to the GPU by value");
-    static_assert(std::is_default_constructible<Problem>::value, "a DDP problem must be default constructible");
-    ModelOps ops;
-    ops.name = Problem::kName;
-    ops.state_dim = Problem::kStateDim;
-    ops.input_dim_max = Problem::kInputDimMax;
-    ops.dynamic_input = 0;
-    ops.param_bytes = sizeof(Problem);
-    ops.default_params = &defaultParams;
-    ops.launch_solve = &launchSolve;
-    ops.input_dims = &inputDims;
-    ops.dt = &dt;
-    ops.kernel_name = &kernelName;
-    ops.launch_mpc_advance = &launchMpcAdvance;
-    ops.has_plant_step = HasPlantStep<Problem>::value ? 1 : 0;
-    ops.wpi_workspace_doubles = &workspaceElems;
-    ops.scalar_bytes = 4;
-    ops.gain_layout = 1;
-    ops.own_problems_supported = [](int, int) { return 1; };
-    return ops;
-  }
-};
-/** Type-erased operations of an fp32 problem type served by the FP64 TILE KERNEL'S FLOAT INSTANTIATION only: the shapes the
-    fp32 tile kernel above does not take (5 <= n <= 15, m <= 8; e.g. the manipulator, n 14, m 7).  Unconstrained solves; a
-    box-constrained solve is refused at launch (the handle reports the HIP error). */
-template<class Problem>
-struct ModelOpsTile64Float
-{
-  static_assert(std::is_same<typename Problem::Scalar, float>::value, "float problem types");
-  static void defaultParams(void * out)
-  {
-    new(out) Problem();
-  }
-  static const char * kernelName(int, const nmpc_hip_ddp_config &)
-  {
-    return "ddp_solve_tile64_kernel";
-  }
-  static hipError_t launchSolve(const void * params, const nmpc_hip_ddp_config & cfg, const DeviceBuffers & buf64, hipStream_t stream)
-  {
-    if(buf64.wpi_ws == nullptr || cfg.with_input_constraint != 0)
-    {
-      return hipErrorNotSupported;
-    }
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    const DeviceBuffersT<float> buf = ModelOpsTile32<Problem>::floatView(buf64);
-    if(buf.params_batch != nullptr)
-    {
-      return launchTile64<Problem, false, true>(problem, cfg, buf, stream);
-    }
-    return launchTile64<Problem, false, false>(problem, cfg, buf, stream);
-  }
-  static hipError_t launchMpcAdvance(const void * params, const DeviceBuffers & buf64, const MpcAdvanceArgs & args, hipStream_t stream)
-  {
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    const DeviceBuffersT<float> buf = ModelOpsTile32<Problem>::floatView(buf64);
-    hipLaunchKernelGGL((mpc_advance_kernel<Problem, float>), dim3(buf.Bp / kLanesPerBlock), dim3(kLanesPerBlock), 0, stream, problem,
-                       buf, args);
-    return hipGetLastError();
-  }
-  static void inputDims(const void *, double, int T, int * out)
-  {
-    for(int i = 0; i < T; i++)
-    {
-      out[i] = Problem::kInputDimMax;
-    }
-  }
-  static double dt(const void * params)
-  {
-    Problem problem;
-    std::memcpy(static_cast<void *>(&problem), params, sizeof(Problem));
-    return static_cast<double>(problem.dt());
-  }
-  static size_t workspaceElems(int T)
-  {
-    return TileSolver64<Problem>::workspaceDoubles(T);
-  }
-  static ModelOps make()
-  {
-    static_assert(std::is_trivially_copyable<Problem>::value, "a DDP problem must be trivially copyable: it is passed to the GPU by value");
-    static_assert(std::is_default_constructible<Problem>::value, "a DDP problem must be default constructible");
-    ModelOps ops;
-    ops.name = Problem::kName;
-    ops.state_dim = Problem::kStateDim;
-    ops.input_dim_max = Problem::kInputDimMax;
-    ops.dynamic_input = 0;
-    ops.param_bytes = sizeof(Problem);
-    ops.default_params = &defaultParams;
-    ops.launch_solve = &launchSolve;
-    ops.input_dims = &inputDims;
-    ops.dt = &dt;
-    ops.kernel_name = &kernelName;
-    ops.launch_mpc_advance = &launchMpcAdvance;
-    ops.has_plant_step = HasPlantStep<Problem>::value ? 1 : 0;
-    ops.wpi_workspace_doubles = &workspaceElems;
-    ops.scalar_bytes = 4;
-    ops.gain_layout = 1;
-    ops.own_problems_supported = [](int, int) { return 1; };
-    return ops;
-  }
-};
 } // namespace hip
 } // namespace nmpc_amd
 
-#define NMPC_AMD_REGISTER_PROBLEM_TILE64_FLOAT(ProblemType) \
-  NMPC_AMD_REGISTER_PROBLEM_WITH(ProblemType, nmpc_amd::hip::ModelOpsTile64Float<ProblemType>)
-
-#define NMPC_AMD_REGISTER_PROBLEM_TILE32(ProblemType) \
-  NMPC_AMD_REGISTER_PROBLEM_WITH(ProblemType, nmpc_amd::hip::ModelOpsTile32<ProblemType>)
+// (registration of fp32 problem types, including the NMPC_AMD_REGISTER_PROBLEM_TILE32 / _TILE64_FLOAT names: model_registry.hpp)
+#include <nmpc_amd/hip/model_registry.hpp>

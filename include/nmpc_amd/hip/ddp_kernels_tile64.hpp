@@ -43,7 +43,6 @@
 // exactly like the lane kernels.
 #pragma once
 
-#include <atomic>
 
 #include <cstring>
 #include <new>
@@ -3668,39 +3667,18 @@ __global__ __launch_bounds__(T64Waves<Problem>::value * 64) void ddp_solve_tile6
   solver.run();
 }
 
-/** Launch helper for model_registry.hpp. */
+/** Launch helper for model_registry.hpp: the handle's knobs (LaunchKnobs; the NMPC_HIP_DDP_TILE64_* variables are developer
+    overrides read when the handle is created) and its device's CU count (knobs.n_cu: one persistent workgroup per CU). */
 template<class Problem, bool kConstrained, bool kOwnProblem>
 inline hipError_t launchTile64(const Problem & problem, const nmpc_hip_ddp_config & cfg, const DeviceBuffersT<typename Problem::Scalar> & buf,
-                               hipStream_t stream)
+                               const LaunchKnobs & knobs, hipStream_t stream)
 {
-  // per device: 0 until the attribute is set and the CU count known (published last, with release order: handles of
-  // several host threads may launch at once — DDPSolverPool, DDPSolverSharded; a second thread repeats the harmless setup)
-  static std::atomic<int> n_cu[64] = {};
-  int dev = 0;
-  if(hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-  {
-    return hipErrorInvalidDevice;
-  }
-  int cus = n_cu[dev].load(std::memory_order_acquire);
-  if(cus == 0)
-  {
-    hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, dev);
-    if(e != hipSuccess)
-    {
-      return e;
-    }
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    n_cu[dev].store(cus, std::memory_order_release);
-  }
-  // the handle's knobs (LaunchKnobs; the NMPC_HIP_DDP_TILE64_* variables are developer overrides read when the handle is created):
   // group: at most g instances per group (tests: full groups on small batches); chunk: at most c timesteps per pass of the model code
   // (1: round 3's schedule); pair = 0: the second step size does not ride in the model wave's upper lanes; adopt = 0: a later step
   // size that is taken is re-rolled (round 3's pass 3); wide = 0: line-search passes as in round 3 (first step size, then the others)
-  const LaunchKnobs knobs = launchKnobs();
   const int cap = knobs.tile64_group, chunk_cap = knobs.tile64_chunk;
   const unsigned no_pair = knobs.tile64_pair ? 0u : 1u, no_adopt = knobs.tile64_adopt ? 0u : 1u, no_wide = knobs.tile64_wide ? 0u : 1u;
-  int grid = cus;
+  int grid = knobs.n_cu;
   if(cap > 0)
   {
     const int groups = (buf.B + cap - 1) / cap; // (the kernel may still choose smaller groups: idle workgroups exit)

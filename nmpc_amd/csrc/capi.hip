@@ -18,6 +18,7 @@
 #include <nmpc_amd/hip/stream_schedule.hpp>
 
 using nmpc_amd::hip::DeviceBuffers;
+using nmpc_amd::hip::KernelPlan;
 using nmpc_amd::hip::ModelOps;
 
 namespace
@@ -83,7 +84,7 @@ struct nmpc_hip_ddp_solver
   bool has_limits = false;
   bool has_shared_limits = false; // nmpc_hip_ddp_set_input_limits was called
   bool solved = false;
-  int last_gain_layout = 0; // ModelOps::gain_layout of the kernel the last solve ran on
+  int last_gain_layout = 0; // KernelPlan::gainLayout() of the kernel the last solve ran on
   hipStream_t stream = nullptr;
   // ring of HIP-event triples {begin, kernel start, end}: one per solve, harvested lazily so that timing a
   // sequence of asynchronous solves never inserts a host synchronisation between them
@@ -150,12 +151,17 @@ struct nmpc_hip_ddp_solver
   float stream_ms = 0;
   bool ragged_ready = false; // all five ragged buffers are allocated and cleared (ensureRagged)
   bool ragged_unavailable = false; // their allocation failed once: the handle keeps to whole-solve launches
-  int ragged_env = 0; // NMPC_HIP_DDP_RAGGED, read once at create: 1 forces the schedule on, -1 off (A/B measurements)
   int last_ragged_rounds = 0; // launches of the last solve (1: an ordinary whole-solve launch)
 };
 
 namespace
 {
+/** The kernel the handle's next solve runs on (one decision per solve: ModelOps::plan). */
+KernelPlan planOf(const nmpc_hip_ddp_solver * s)
+{
+  return s->ops->plan(s->knobs, s->B, s->cfg, s->d_params_batch != nullptr);
+}
+
 template<class T>
 int devAlloc(T ** p, size_t count)
 {
@@ -492,10 +498,10 @@ namespace
     done after 14 iterations, a percent runs for hundreds: compaction pays while the prefix shrinks fast; once the running instances
     fit a few workgroups (64 iterations: 137 of 4096) another boundary only costs its ~90 us of launch gaps [measured: ten launches
     per 500-iteration solve 829, whole-solve launch 858 batch-iterations/s on a lone stream]. */
-bool raggedRounds(const nmpc_hip_ddp_solver * s, std::vector<int> * caps)
+bool raggedRounds(const nmpc_hip_ddp_solver * s, const KernelPlan & plan, std::vector<int> * caps)
 {
-  const int mode = s->ragged_env != 0 ? s->ragged_env : s->cfg.ragged_schedule;
-  if(mode < 0 || s->ragged_unavailable || s->elem != 8 || s->ops->resumable_supported == nullptr)
+  const int mode = s->knobs.ragged != 0 ? s->knobs.ragged : s->cfg.ragged_schedule;
+  if(mode < 0 || s->ragged_unavailable || !plan.resumable)
   {
     return false;
   }
@@ -506,10 +512,6 @@ bool raggedRounds(const nmpc_hip_ddp_solver * s, std::vector<int> * caps)
   // means: solves queued through nmpc_hip_ddp_solve_async (DDPSolverBatch::solveAsync, the C++ DDPSolverPool); synchronous solve(),
   // solve_device() and the ticks of mpc_run() take one launch.  Pools over solve_device ask with 1 (nmpc_amd.DDPSolverPool does).
   if(mode == 0 && (!s->queued_solve || s->cfg.max_iter < 64))
-  {
-    return false;
-  }
-  if(!s->ops->resumable_supported(s->B, s->cfg, s->d_params_batch ? 1 : 0))
   {
     return false;
   }
@@ -629,7 +631,8 @@ nmpc_amd::hip::SwapTable swapTable(const nmpc_hip_ddp_solver * s)
 
 /** The ragged-convergence schedule: resumable launches of iterations (caps[r-1], caps[r]] with a compaction between them, then
     the recorded swaps replayed in reverse.  All on stream st, no host round trip. */
-int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, const std::vector<int> & caps, bool * fell_back)
+int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, const KernelPlan & plan, const std::vector<int> & caps,
+                 bool * fell_back)
 {
   *fell_back = false;
   if(ensureRagged(s) != NMPC_HIP_OK)
@@ -645,7 +648,7 @@ int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, con
   int * n_swaps = s->d_ragged_words + R + 1;
   const nmpc_amd::hip::SwapTable tab = swapTable(s);
   const dim3 swap_grid(static_cast<unsigned>((s->Bp / 2 + 63) / 64), 64);
-  const int wg_size = std::strcmp(s->ops->kernel_name(s->B, s->cfg), "ddp_solve_quad_kernel") == 0 ? 16 : 64;
+  const int wg_size = plan.swapGroup();
   buf.resume = s->d_resume;
   hipLaunchKernelGGL(nmpc_amd::hip::ragged_init_kernel, dim3(1), dim3(64), 0, st, n_active, s->B);
   int swapped_rounds = 0; // rounds whose compaction swaps are queued: they are replayed in reverse whatever happens after them
@@ -655,7 +658,7 @@ int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, con
     buf.n_active = n_active + r;
     buf.iter_begin = (r == 0) ? 1 : caps[r - 1] + 1;
     buf.iter_end = caps[r];
-    le = s->ops->launch_solve(s->params.data(), s->cfg, buf, st);
+    le = s->ops->launch_solve(s->params.data(), plan, s->knobs, s->cfg, buf, st);
     if(le != hipSuccess)
     {
       break;
@@ -691,7 +694,7 @@ int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, con
 
 /** A queue of n_total instances through the handle's B slots (stream_schedule.hpp).  in / out: device arrays in the reference
     layouts.  span: iterations per round. */
-int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const nmpc_amd::hip::StreamArrays & io, int n_total, int span)
+int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & plan, const nmpc_amd::hip::StreamArrays & io, int n_total, int span)
 {
   using namespace nmpc_amd::hip;
   int rc = ensureRagged(s);
@@ -712,7 +715,6 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const nmpc_amd::hip::S
     }
     NMPC_HIP_TRY(hipDeviceSynchronize()); // (devAlloc's clears are ordered on the NULL stream)
   }
-  nmpc_amd::hip::ScopedKnobs knobs_guard(&s->knobs);
   int * w = s->d_stream_words;
   DeviceBuffers buf = makeBuffers(s);
   buf.resume = s->d_resume;
@@ -722,7 +724,7 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const nmpc_amd::hip::S
   buf.iter_end = span;
   const SwapTable tab = swapTable(s);
   const dim3 swap_grid(static_cast<unsigned>((s->Bp / 2 + 63) / 64), 64);
-  const int wg_size = std::strcmp(s->ops->kernel_name(s->B, s->cfg), "ddp_solve_quad_kernel") == 0 ? 16 : 64;
+  const int wg_size = plan.swapGroup();
   const dim3 fill_grid(static_cast<unsigned>(s->B), static_cast<unsigned>((s->T * s->MM + 1023) / 1024));
   struct TimingEvents
   {
@@ -802,7 +804,7 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const nmpc_amd::hip::S
     }
     for(int k = 0; k < kBlock && le == hipSuccess; k++, rounds++)
     {
-      le = s->ops->launch_solve(s->params.data(), s->cfg, buf, st);
+      le = s->ops->launch_solve(s->params.data(), plan, s->knobs, s->cfg, buf, st);
       if(le != hipSuccess)
       {
         break;
@@ -859,7 +861,7 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
 {
   // timed = false: no event records around this solve (the inner ticks of the device-resident receding-horizon loop: three
   // event packets per 0.6 ms tick were 1 - 2 % of the loop; computationDuration() reports the loop's last solve)
-  nmpc_amd::hip::ScopedKnobs knobs_guard(&s->knobs);
+  const KernelPlan plan = planOf(s);
   s->last_stream = st;
   const int slot = static_cast<int>(s->n_solves % nmpc_hip_ddp_solver::kEvPool);
   if(timed)
@@ -894,12 +896,12 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
   }
   DeviceBuffers buf = makeBuffers(s);
   std::vector<int> caps;
-  s->last_gain_layout = s->ops->gain_layout_of ? s->ops->gain_layout_of(s->B, s->cfg.with_input_constraint != 0 ? 1 : 0) : s->ops->gain_layout;
+  s->last_gain_layout = plan.gainLayout();
   s->last_ragged_rounds = 1;
-  bool whole_solve = !raggedRounds(s, &caps);
+  bool whole_solve = !raggedRounds(s, plan, &caps);
   if(!whole_solve)
   {
-    int rrc = launchRagged(s, st, buf, caps, &whole_solve);
+    int rrc = launchRagged(s, st, buf, plan, caps, &whole_solve);
     if(rrc != NMPC_HIP_OK)
     {
       return rrc;
@@ -907,13 +909,14 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
   }
   if(whole_solve)
   {
-    const hipError_t le = s->ops->launch_solve(s->params.data(), s->cfg, buf, st);
+    const hipError_t le = s->ops->launch_solve(s->params.data(), plan, s->knobs, s->cfg, buf, st);
     if(le == hipErrorNotSupported)
     {
       return fail(NMPC_HIP_ERR_RUNTIME,
-                  s->elem == 4 ? "the fp32 tile kernel has no gain workspace on this handle (allocation failed at create)"
-                               : "per-instance problem objects (set_model_params_batch) are served by the model's default kernel "
-                                 "only; this solve needs the single-wavefront kernel");
+                  plan.needsWorkspace() ? std::string(plan.kernelName()) + " has no gain workspace on this handle (allocation failed at create)"
+                  : plan.own_problems   ? "per-instance problem objects (set_model_params_batch) are served by the model's default kernel "
+                                          "only; this solve needs the single-wavefront kernel"
+                                        : std::string(plan.kernelName()) + " has no instantiation for this solve");
     }
     NMPC_HIP_TRY(le);
   }
@@ -932,9 +935,9 @@ extern "C"
 {
   int nmpc_hip_ddp_register_model(const ModelOps * ops)
   {
-    if(!ops || !ops->name)
+    if(!ops || ops->abi != nmpc_amd::hip::kModelOpsAbi || !ops->name)
     {
-      return NMPC_HIP_ERR_INVALID_ARGUMENT;
+      return NMPC_HIP_ERR_INVALID_ARGUMENT; // (a table of another layout: compiled against an older model_ops.hpp)
     }
     if(findModel(ops->name))
     {
@@ -1108,12 +1111,12 @@ extern "C"
     s->elem = m->scalar_bytes;
     nmpc_hip_ddp_default_config(&s->cfg);
     s->cfg.horizon_steps = horizon_steps;
-    if(const char * e = std::getenv("NMPC_HIP_DDP_RAGGED")) // (read once per handle: A/B measurements of the ragged schedule)
-    {
-      s->ragged_env = (std::strcmp(e, "0") == 0) ? -1 : 1;
-    }
     s->knobs = nmpc_amd::hip::LaunchKnobs::fromEnvironment(); // developer overrides: read ONCE, here (not on the launch path)
-    nmpc_amd::hip::ScopedKnobs knobs_guard(&s->knobs);
+    int n_cu = 0;
+    if(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0)
+    {
+      s->knobs.n_cu = n_cu;
+    }
     s->params.resize(m->param_bytes);
     m->default_params(s->params.data());
     for(int i = 0; i < nmpc_amd::hip::kMaxInputDim; i++)
@@ -1147,24 +1150,19 @@ extern "C"
     chk(devAlloc(&s->d_qp_free, T * Bp));
     chk(devAlloc(&s->d_input_dim, T * Bp));
     chk(devAlloc(&s->d_phase_ticks, 4 * Bp));
-    // (NMPC_HIP_DDP_NO_WORKSPACE=1: developer switch for the tests of the path a failed workspace allocation takes)
-    const char * no_ws = std::getenv("NMPC_HIP_DDP_NO_WORKSPACE");
-    if(no_ws && std::strcmp(no_ws, "0") != 0)
-    {
-      s->knobs.have_workspace = 0;
-    }
-    else if(m->wpi_workspace_doubles(s->T) > 0)
+    // (knobs.have_workspace 0 already: NMPC_HIP_DDP_NO_WORKSPACE, the tests of the path a failed workspace allocation takes)
+    const size_t ws_elems = m->wpi_workspace_doubles(s->knobs, s->T);
+    if(s->knobs.have_workspace != 0 && ws_elems > 0)
     {
       // wave-per-instance kernel (9 <= n <= 16): materialised derivatives, gains and one candidate trajectory per
       // step size, per instance; quad-kernel shapes: three candidate trajectories per instance, tile-major (the line
       // search's fan-out scratch).  No memset: the kernels write everything they read.
-      if(hipMalloc(reinterpret_cast<void **>(&s->d_wpi_ws),
-                   m->wpi_workspace_doubles(s->T) * static_cast<size_t>(s->Bp) * static_cast<size_t>(s->elem))
+      if(hipMalloc(reinterpret_cast<void **>(&s->d_wpi_ws), ws_elems * static_cast<size_t>(s->Bp) * static_cast<size_t>(s->elem))
          != hipSuccess)
       {
         (void)hipGetLastError();
         s->d_wpi_ws = nullptr; // not enough memory for the workspace: the lane-per-instance kernel needs none
-        s->knobs.have_workspace = 0; // (kernel_name / gain_layout_of / launch_solve then choose among the kernels that need none)
+        s->knobs.have_workspace = 0; // (plan() then chooses among the kernels that need none)
       }
     }
     if(rc == NMPC_HIP_OK)
@@ -1359,10 +1357,10 @@ extern "C"
       }
       return NMPC_HIP_OK;
     }
-    nmpc_amd::hip::ScopedKnobs knobs_guard(&s->knobs);
-    if(s->ops->own_problems_supported && !s->ops->own_problems_supported(s->B, s->cfg.with_input_constraint != 0 ? 1 : 0))
+    const KernelPlan plan = s->ops->plan(s->knobs, s->B, s->cfg, true);
+    if(!nmpc_amd::hip::familyInfo(plan.family).own_problems)
     {
-      return fail(NMPC_HIP_ERR_RUNTIME, std::string("the kernel this handle solves on (") + s->ops->kernel_name(s->B, s->cfg)
+      return fail(NMPC_HIP_ERR_RUNTIME, std::string("the kernel this handle solves on (") + plan.kernelName()
                                             + ") has no instantiation with one problem object per instance");
     }
     const size_t pb = s->ops->param_bytes;
@@ -1743,7 +1741,8 @@ extern "C"
       return fail(NMPC_HIP_ERR_RUNTIME, "with_input_constraint is set but no input limits were given "
                                         "(setInputLimitsFunc, DDPSolver.h:282-285)");
     }
-    if(s->elem != 8 || s->ops->resumable_supported == nullptr || !s->ops->resumable_supported(s->B, s->cfg, s->d_params_batch ? 1 : 0))
+    const KernelPlan plan = planOf(s);
+    if(!plan.resumable)
     {
       return fail(NMPC_HIP_ERR_RUNTIME, "a streamed solve needs a kernel family with resumable launches: the quad / two-wave kernels "
                                         "(n <= 4, one input, fp64) with a shared problem object");
@@ -1795,7 +1794,7 @@ extern "C"
     }
     NMPC_HIP_TRY(hipMemcpyAsync(d_x0, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
     NMPC_HIP_TRY(hipMemcpyAsync(d_u, u_init, n_u * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    int rc = launchStream(s, s->stream, io, n_instances, span);
+    int rc = launchStream(s, s->stream, plan, io, n_instances, span);
     if(rc != NMPC_HIP_OK)
     {
       return rc;
@@ -2011,8 +2010,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle or output pointer");
     }
-    nmpc_amd::hip::ScopedKnobs knobs_guard(&s->knobs);
-    *name = s->ops->kernel_name(s->B, s->cfg);
+    *name = planOf(s).kernelName();
     return NMPC_HIP_OK;
   }
 
@@ -2024,8 +2022,7 @@ extern "C"
     }
     nmpc_amd::hip::LaunchKnobs k = s->knobs;
     k.dispatch_batch = 0;
-    nmpc_amd::hip::ScopedKnobs knobs_guard(&k);
-    *name = s->ops->kernel_name(batch, s->cfg);
+    *name = s->ops->plan(k, batch, s->cfg, s->d_params_batch != nullptr).kernelName();
     return NMPC_HIP_OK;
   }
 
@@ -2035,38 +2032,16 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle or kernel name");
     }
-    static const char * const known[] = {"auto", "1w", "2w", "quad", "wpi", "tile64", "tile32"};
-    // (also accepted: the names nmpc_hip_ddp_kernel_name reports)
-    static const char * const reported[][2] = {{"ddp_solve_tpi_kernel", "1w"},        {"ddp_solve_tpi2w_kernel", "2w"},
-                                               {"ddp_solve_quad_kernel", "quad"},     {"ddp_solve_wpi_kernel", "wpi"},
-                                               {"ddp_solve_tile64_kernel", "tile64"}, {"ddp_solve_tile32_kernel", "tile32"}};
-    const char * pick = nullptr;
-    for(const char * k : known)
+    // (a short name, "auto", or one of the names nmpc_hip_ddp_kernel_name reports)
+    if(!nmpc_amd::hip::familyByName(name, &s->knobs.pin))
     {
-      if(std::strcmp(k, name) == 0)
+      std::string known = "auto";
+      for(const auto & f : nmpc_amd::hip::kFamilies)
       {
-        pick = k;
+        known += std::string(", ") + f.pin;
       }
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, std::string("unknown kernel family: ") + name + " (" + known + ")");
     }
-    for(const auto & r : reported)
-    {
-      if(std::strcmp(r[0], name) == 0)
-      {
-        pick = r[1];
-      }
-    }
-    if(!pick)
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, std::string("unknown kernel family: ") + name
-                                                     + " (auto, 1w, 2w, quad, wpi, tile64, tile32)");
-    }
-    nmpc_amd::hip::LaunchKnobs k = s->knobs;
-    std::memset(k.kernel, 0, sizeof(k.kernel));
-    if(std::strcmp(pick, "auto") != 0)
-    {
-      std::strncpy(k.kernel, pick, sizeof(k.kernel) - 1);
-    }
-    s->knobs = k;
     return NMPC_HIP_OK;
   }
 

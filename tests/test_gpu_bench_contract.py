@@ -117,7 +117,7 @@ def test_c4_runs_in_fp32_on_a_tile_kernel():
     # the kept fraction of the fp32 parity (decisions equal to the float oracle's) rides in the line
     print("c4 decisions equal to the fp32 oracle's:", d["cpu_baseline"]["gpu_decisions_agree_frac"])
     assert d["cpu_baseline"]["gpu_decisions_checked"] == 256 and d["cpu_baseline"]["gpu_decisions_agree_frac"] >= 0.5
-    # (eight iterations of a full chip: the tile kernel's float instantiation, ModelOpsTile32::useTile64Float)
+    # (eight iterations of a full chip: the tile kernel's float instantiation, ModelOpsFor::plan)
     assert d["roofline"]["kernel"] == "ddp_solve_tile64_kernel<quadrotor_f32>" and "float instantiation" in d["config"]["lane_mapping"]
     # the headline is the threshold an fp32 cost can resolve; the reference's default rides along as the secondary number
     assert d["config"]["cost_update_thre"] == 1e-3 and "cost_update_thre = 0.001" in d["config"]["workload"]

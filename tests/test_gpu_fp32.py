@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 #: the kernel an UNCONSTRAINED quadrotor_f32 solve runs on when NMPC_HIP_DDP_KERNEL forces it: the fp32 tile kernel, or the fp64 tile
 #: kernel's float instantiation (ddp_kernels_tile64.hpp with v_mfma_f32_16x16x4: round 4).  Unforced the choice is per launch
-#: (ModelOpsTile32::useTile64Float: the float instantiation below 8192 instances, and on full chips with a cost_update_thre >= 5e-4 —
+#: (ModelOpsFor::plan: the float instantiation below 8192 instances, and on full chips with a cost_update_thre >= 5e-4 —
 #: test_fp32_kernel_dispatch).  Box-constrained solves and cartpole_f32 (n = 4) run on ddp_solve_tile32_kernel either way.
 F32_KERNEL = {"tile32": "ddp_solve_tile32_kernel", "tile64": "ddp_solve_tile64_kernel"}
 
@@ -33,7 +33,7 @@ def f32_kernel(request, monkeypatch):
 
 
 def test_fp32_kernel_dispatch(monkeypatch):
-    """Which kernel an fp32 solve runs on when nothing forces it (ddp_kernels_tile32.hpp::useTile64Float, measured in
+    """Which kernel an fp32 solve runs on when nothing forces it (model_registry.hpp, ModelOpsFor::plan, measured in
     profiles/r04_c4_dispatch_sweep.txt)."""
     import nmpc_amd
 

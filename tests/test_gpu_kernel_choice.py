@@ -1,5 +1,7 @@
 """Kernel choice through the API: nmpc_hip_ddp_set_kernel / set_dispatch_batch / kernel_name_for_batch and their
 mirrors.  The environment variables are developer overrides read ONCE, when a handle is created — not on the launch path."""
+import os
+
 import numpy as np
 import pytest
 
@@ -83,3 +85,73 @@ def test_without_the_workspace_the_lane_kernels_take_the_solve(monkeypatch):
     assert scaled_err(s.X(), ref.X) < 1e-9 and scaled_err(s.Kfb(), ref.K) < 1e-8
     t = make_solver(wl, max_iter=4)
     assert t.kernelName() == "ddp_solve_tile64_kernel"
+
+
+# ---- the dispatch table: every registered DDP problem type, every pin, with and without the workspace ----------------------------------
+# tests/golden/kernel_choice.txt was recorded from the library before the kernel choice moved into one plan per solve
+# (ModelOpsFor::plan, include/nmpc_amd/hip/model_registry.hpp); the decision must not have moved for any combination.
+TABLE_MODELS = ("cartpole", "bipedal", "vertical", "centroidal", "quadrotor", "manipulator", "planar_vtol", "cartpole_f32",
+                "quadrotor_f32", "manipulator_f32")
+TABLE_BATCHES = (16, 63, 64, 512, 1024, 1025, 4096, 4097, 6143, 6144, 8191, 8192, 16384)
+TABLE_PINS = ("auto", "1w", "2w", "quad", "wpi", "tile64", "tile32")
+TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_choice.txt")
+
+
+def dispatch_table():
+    """One line per (model, constrained, cost_update_thre, pin, workspace): whether set_model_params_batch is accepted at the handle's
+    batch (64), then the family kernel_name_for_batch reports for every batch of TABLE_BATCHES (ddp_solve_<family>_kernel)."""
+    import ctypes as C
+
+    from nmpc_amd import _capi
+    L = _capi.load()
+    lines = []
+    for ws in (1, 0):
+        for model in TABLE_MODELS:
+            if ws:
+                os.environ.pop("NMPC_HIP_DDP_NO_WORKSPACE", None)
+            else:
+                os.environ["NMPC_HIP_DDP_NO_WORKSPACE"] = "1"
+            try:
+                prob = nmpc_amd.make_problem(model)
+                s = nmpc_amd.DDPSolverBatch(prob, 64)
+                s.config().print_level = 0
+                s.config().horizon_steps = 20
+                s.kernelName()  # (creates the handle: the environment is read here)
+            finally:
+                os.environ.pop("NMPC_HIP_DDP_NO_WORKSPACE", None)
+            for con in (0, 1):
+                for thre in ((1e-7, 1e-3) if model.endswith("_f32") else (None,)):
+                    for pin in TABLE_PINS:
+                        s.config().with_input_constraint = bool(con)
+                        if thre is not None:
+                            s.config().cost_update_thre = thre
+                        s.setKernel(pin)
+                        names = [s.kernelNameForBatch(b)[len("ddp_solve_"):-len("_kernel")] for b in TABLE_BATCHES]
+                        raw = bytes(prob.blob) * 64
+                        own = L.nmpc_hip_ddp_set_model_params_batch(s._h, raw, C.sizeof(prob.blob)) == _capi.OK
+                        _capi.check(L.nmpc_hip_ddp_set_model_params_batch(s._h, None, 0))
+                        key = f"{model} con={con} thre={'-' if thre is None else f'{thre:g}'} pin={pin} ws={ws}"
+                        lines.append(f"{key} own={int(own)} : {' '.join(names)}")
+            s.close()
+    return lines
+
+
+def test_dispatch_table_matches_the_recorded_one():
+    with open(TABLE_PATH) as f:
+        want = [ln.rstrip("\n") for ln in f if ln.strip() and not ln.startswith("#")]
+    assert dispatch_table() == want
+
+
+def test_stream_check_uses_the_handles_knobs(monkeypatch):
+    """solve_stream asks the handle's own plan whether its family has resumable launches: a handle pinned to the single-wavefront
+    kernel is refused up front, and a variable set after create does not change an unpinned handle's answer."""
+    wl = workloads.cartpole_batch(B=300, T=30, seed=5)
+    s = make_solver(wl, max_iter=20)
+    s.setKernel("1w")
+    with pytest.raises(RuntimeError, match=r"nmpc_hip_ddp -2\].*resumable"):
+        s.solveStream(wl.t0, wl.x0, wl.u_init)
+    t = make_solver(wl, max_iter=20)
+    t.kernelName()  # (creates the handle)
+    monkeypatch.setenv("NMPC_HIP_DDP_KERNEL", "1w")
+    r = t.solveStream(wl.t0, wl.x0, wl.u_init)
+    assert r.iters.shape == (wl.B,) and (r.iters > 0).all()

@@ -1058,7 +1058,7 @@ def test_planar_vtol_box_constrained_on_the_tile_kernel(monkeypatch):
 
 
 def test_small_models_leave_the_tile_kernel_at_large_batches(monkeypatch):
-    """ModelOpsFor::kLaneKeepsUp (n (n + m) <= 48: planar VTOL): up to 1024 instances (BoxQP: 6143) the tile kernel, above the lane
+    """ModelOpsFor::plan, kLaneKeepsUp (n (n + m) <= 48: planar VTOL): up to 1024 instances (BoxQP: 6143) the tile kernel, above the lane
     kernel, whose time does not grow with the batch (profiles/r05_lane_vs_tile_ab.txt) — same decisions, values to TOL, oracle
     parity on either side of the switch; a handle that pins the tile kernel keeps it; the quadrotor (n (n + m) = 192) never switches."""
     import nmpc_amd

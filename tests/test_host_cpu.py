@@ -96,6 +96,26 @@ def test_misuse_is_reported_not_crashed():
     assert L.nmpc_hip_ddp_set_input_limits_batch(None, None, None) == _capi.ERR_INVALID_ARGUMENT
 
 
+def test_register_model_refuses_another_layout():
+    """ModelOps starts with a layout word (include/nmpc_amd/hip/model_ops.hpp, kModelOpsAbi): a model library compiled against
+    another version of the header is refused instead of being misread."""
+    hdr = open(os.path.join(ROOT, "include", "nmpc_amd", "hip", "model_ops.hpp")).read()
+    abi = int(re.search(r"constexpr int kModelOpsAbi = (\d+);", hdr).group(1))
+
+    class Ops(C.Structure):
+        _fields_ = [("abi", C.c_int), ("name", C.c_char_p), ("rest", C.c_void_p * 32)]
+
+    L = _capi.load()
+    register = L.nmpc_hip_ddp_register_model
+    register.argtypes, register.restype = [C.c_void_p], C.c_int
+    n = L.nmpc_hip_ddp_model_count()
+    for wrong in (abi + 1, abi - 1, 0):
+        ops = Ops(abi=wrong, name=b"layout_probe")
+        assert register(C.byref(ops)) == _capi.ERR_INVALID_ARGUMENT
+    assert register(None) == _capi.ERR_INVALID_ARGUMENT
+    assert L.nmpc_hip_ddp_model_count() == n
+
+
 def test_no_cpu_fallback_without_a_gpu():
     from conftest import HAVE_GPU
     if HAVE_GPU:
