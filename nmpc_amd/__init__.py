@@ -7,3 +7,4 @@ from .ddp import (ComputationDuration, Configuration, ControlData, DDPSolverBatc
                   StreamResult, TraceData, request_hw_queues)
 from .models import (DDPProblemBipedal, DDPProblemCartPole, DDPProblemCartPoleF32, DDPProblemCentroidalMotion,  # noqa: F401
                      DDPProblemManipulator, DDPProblemManipulatorF32, DDPProblemQuadrotor, DDPProblemVerticalMotion, make_problem)
+from .cgmres import CgmresProblem, CgmresProblemCartPole, CgmresProblemSemiactiveDamper, CgmresSolverBatch  # noqa: F401
