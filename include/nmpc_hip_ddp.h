@@ -288,9 +288,13 @@ extern "C"
                            double * t_final);
 
   /** Name of the gfx950 kernel the next solve of this handle launches (as rocprofv3 --kernel-trace lists it, without
-      template arguments): "ddp_solve_tpi2w_kernel" (master + helper wavefront per 64 instances, LDS-staged; chosen
-      when the model's LDS records fit) or "ddp_solve_tpi_kernel" (one wavefront per 64 instances; also forced by the
-      environment variable NMPC_HIP_DDP_KERNEL=1w).  No reference counterpart: diagnostics for profiles / bench.py. */
+      template arguments): the kernel symbol of one of the six families of kFamilies (include/nmpc_amd/hip/model_ops.hpp),
+      "ddp_solve_tpi_kernel" (1w: one wavefront per 64 instances), "ddp_solve_tpi2w_kernel" (2w: master + helper wavefront,
+      LDS-staged), "ddp_solve_quad_kernel" (quad: matrix-core backward pass, 16 instances per workgroup),
+      "ddp_solve_wpi_kernel" (wpi: one wavefront per instance), "ddp_solve_tile64_kernel" (tile64: groups of instances per
+      workgroup, fp64 and float) or "ddp_solve_tile32_kernel" (tile32: the fp32 tile kernel).  The family is chosen per solve
+      (ModelOpsFor::family) or pinned by nmpc_hip_ddp_set_kernel / NMPC_HIP_DDP_KERNEL.  No reference counterpart:
+      diagnostics for profiles / bench.py. */
   int nmpc_hip_ddp_kernel_name(nmpc_hip_ddp_handle h, const char ** name);
 
   /** The same for a handle of `batch` instances with this handle's problem type, Configuration and kernel choice: what a sharding

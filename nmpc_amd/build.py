@@ -205,8 +205,79 @@ def build_fuzz(seed: int = 1, force: bool = False, verbose: bool = False) -> str
                          force=force, verbose=verbose)
 
 
+TEST_MODEL_DIR = os.path.join(ROOT, "tests", "cpp")
+TEST_MODEL_SOURCES = ("boxqp_probe_models.hip",)
+TEST_MODEL_HEADERS = ("boxqp_probe.hpp",)
+TEST_MODEL_PROBES = 5  # NMPC_TEST_PROBE_COUNT of boxqp_probe_models.hip
+
+
+def test_models_path() -> str:
+    return os.path.join(LIB_DIR, "testmodels", "libnmpc_test_models.so")
+
+
+def build_test_models(force: bool = False, verbose: bool = False) -> str:
+    """The test-only problem types of tests/cpp (the BoxQP probes of tests/test_gpu_boxqp_known_answers.py), compiled for gfx950 into
+    nmpc_amd/lib/testmodels/libnmpc_test_models.so.  Not part of the product library: it registers nothing itself but exports its
+    operations tables (nmpc_test_model_ops), which a test hands to nmpc_hip_ddp_register_model of the library it loaded.  Rebuilt when
+    a source or header is newer than the library."""
+    lib = test_models_path()
+    srcs = [os.path.join(TEST_MODEL_DIR, s) for s in TEST_MODEL_SOURCES]
+    deps = srcs + [os.path.join(TEST_MODEL_DIR, h) for h in TEST_MODEL_HEADERS] + _headers()
+    if not force and os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps if os.path.exists(d)):
+        return lib
+    obj_dir = os.path.join(os.path.dirname(lib), "obj")
+    os.makedirs(obj_dir, exist_ok=True)
+    cc = hipcc()
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}"]
+    objs, procs = [], []
+    # one translation unit per probe (-DNMPC_TEST_PROBE=<i>) so that they compile in parallel, plus the index without it
+    units = [(src, []) for src in srcs] + [(srcs[0], ["-DNMPC_TEST_PROBE=%d" % i]) for i in range(TEST_MODEL_PROBES)]
+    for src, defs in units:
+        obj = os.path.join(obj_dir, os.path.basename(src).replace(".hip", "".join("_" + d.split("=")[-1] for d in defs) + ".o"))
+        objs.append(obj)
+        cmd = [cc] + flags + defs + ["-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    for cmd, p in procs:
+        out, _ = p.communicate()
+        if p.returncode != 0:
+            raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + out)
+    cmd = [cc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + objs + ["-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("link failed:\n" + r.stdout)
+    return lib
+
+
+class TestModelsBuild:
+    """build_test_models() on a background thread (its work is hipcc child processes): start it, build something else, then wait(),
+    which returns the library's path or raises what the build raised."""
+
+    def __init__(self, force: bool = False):
+        import threading
+        self._out = {}
+
+        def run():
+            try:
+                self._out["path"] = build_test_models(force=force)
+            except BaseException as e:  # re-raised by wait()
+                self._out["error"] = e
+
+        self._thread = threading.Thread(target=run, name="build_test_models", daemon=True)
+        self._thread.start()
+
+    def wait(self) -> str:
+        self._thread.join()
+        if "error" in self._out:
+            raise self._out["error"]
+        return self._out["path"]
+
+
 if __name__ == "__main__":
-    if "--fuzz" in sys.argv:
+    if "--test-models" in sys.argv:
+        print(build_test_models(force="--force" in sys.argv, verbose=True))
+    elif "--fuzz" in sys.argv:
         k = sys.argv.index("--fuzz")
         seeds = [int(a) for a in sys.argv[k + 1:] if a.isdigit()] or [1]
         for sd in seeds:

@@ -226,6 +226,55 @@ def test_centroidal_large_input_dimension():
     assert set(np.unique(s.inputDimList())) == {0, 16}
 
 
+def test_centroidal_box_constrained_on_the_lane_kernel():
+    """The shipped dispatch row no other test solves: centroidal motion (n 9, inputDim(t) in {16, 0}) with input limits runs on the
+    single-wave lane kernel, whose run-time m boxQP then works at m = 16, and whose warm start (k of the next timestep only when its
+    size matches, DDPSolver.hpp:452-467) meets the 16 -> 0 -> 16 switches of the flight phase.  96 instances (one full and one partial
+    wavefront), T = 60 across the switch, unilateral [0, 80] ridge forces: the lower bounds bind on the unloaded ridges and the upper
+    ones under the landing impact (with the upper bound lifted the oracle's free sets change).
+
+    The QPs are degenerate: sixteen ridge forces make one six-dimensional wrench, so Quu's small eigenvalues are the input weight, and
+    BoxQP stops at a gradient of 1e-8 (qp_grad_thre), which leaves k undetermined by ~1e-8 / weight.  Measured on the oracle alone:
+    with the reference's weight 1e-6, a 1e-15 relative perturbation of x0 changes the alpha history of 6 % of the instances (and the
+    kernel's rounding flipped one step size of one instance); with weight 1e-3 every decision is stable under 1e-15 .. 1e-11
+    perturbations.  So the weight is 1e-3 here, and everything is checked at the bar of this file on every instance (measured: X, U,
+    cost within 2e-14, k 9e-14, K 4e-13), BoxQP retval and free set per timestep against single-instance oracle solves, entries of U
+    beyond inputDim(t) exactly 0."""
+    import nmpc_amd
+    from nmpc_amd import workloads
+    wl = workloads.centroidal_batch(B=96, T=60, seed=5)
+    lo, up = np.zeros(16), np.full(16, 80.0)
+    s = nmpc_amd.DDPSolverBatch(nmpc_amd.DDPProblemCentroidalMotion(running_u=1e-3), wl.B)
+    c = s.config()
+    c.print_level, c.horizon_steps, c.max_iter, c.with_input_constraint = 0, wl.T, 6, True
+    s.setInputLimits(lo, up)
+    assert s.kernelName() == "ddp_solve_tpi_kernel"
+    s.solve(wl.t0, wl.x0, wl.u_init)
+    p = oracle.default_params("centroidal", running_u=1e-3)
+    ocfg = oracle.default_config(horizon_steps=wl.T, max_iter=6, with_input_constraint=1)
+    ref = oracle.solve_batch(wl.model, ocfg, wl.x0, wl.u_init, t0=wl.t0, params=p, lower=lo, upper=up, n_threads=8, want_alpha_hist=True)
+    assert set(np.unique(ref.status)) >= {1}
+    check_against_oracle(wl, s, ref)
+    dims = s.inputDimList()
+    assert set(np.unique(dims)) == {0, 16}
+    assert np.all(s.U()[dims == 0] == 0.0)  # entries beyond inputDim(t) are zero
+    qret, qfree = s.qpRetval(), s.qpFreeMask()
+    n_clamped, seen_m, upper_binds = 0, set(), False
+    for b in range(0, wl.B, 9):
+        r = oracle.solve(wl.model, ocfg, wl.x0[b], wl.u_init[b], t0=float(wl.t0[b]), params=p, lower=lo, upper=up)
+        np.testing.assert_array_equal(dims[b], r.m_list)
+        np.testing.assert_array_equal(qret[b], r.qp_retval)
+        np.testing.assert_array_equal(qfree[b], r.qp_free_mask)
+        seen_m |= set(int(m) for m in r.m_list)
+        n_clamped += sum(16 - bin(int(f)).count("1") for f, m in zip(r.qp_free_mask, r.m_list) if m == 16)
+        if not upper_binds:
+            r1 = oracle.solve(wl.model, ocfg, wl.x0[b], wl.u_init[b], t0=float(wl.t0[b]), params=p, lower=lo, upper=np.full(16, 1e30))
+            upper_binds = not np.array_equal(r1.qp_free_mask, r.qp_free_mask)
+    assert n_clamped > 0, "the sample never hit the bounds: the constrained branch was not exercised"
+    assert seen_m == {0, 16}, seen_m
+    assert upper_binds, "no upper bound binds in the sample"
+
+
 def test_quadrotor_and_manipulator():
     """Builder-defined models of BASELINE configs 4 and 5 (fp64), parity vs the oracle's own statement."""
     from nmpc_amd import workloads
