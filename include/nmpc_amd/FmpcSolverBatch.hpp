@@ -7,6 +7,11 @@
 // problem TYPE must have been compiled into a gfx950 code object and registered (NMPC_AMD_REGISTER_FMPC_PROBLEM,
 // <nmpc_amd/hip/fmpc_ops.hpp>); the problem OBJECT passed here is copied to the solver at every solve(), so mutating it
 // between solves behaves as with the reference's shared_ptr.
+//
+// Time-varying dimensions (Problem::kDynamicInput / kDynamicIneq): the vectors of Variable have run-time sizes; solve() checks that
+// u_list[i], s_list[i], nu_list[i] of an initial guess have inputDim(t + i dt) / ineqDim(t + i dt) entries (std::runtime_error
+// otherwise, as FmpcSolver.hpp:314-344), and variable() / feedbackGain() return them sized with the dimensions of the last solve.
+// At the C-ABI every step is padded to the capacity (include/nmpc_hip_fmpc.h).
 #pragma once
 
 #include <fstream>
@@ -202,6 +207,7 @@ public:
     }
     check(nmpc_hip_fmpc_set_problem(handle_, problems.data(), problems.size() * sizeof(Problem), 1));
     own_problems_ = true;
+    problems_ = problems;
   }
 
   /** \brief Solve optimization for every instance (FmpcSolver::solve, FmpcSolver.h:283).
@@ -225,6 +231,10 @@ public:
     }
     if(!initial_variable.empty())
     {
+      if constexpr(Problem::kDynamicInput || Problem::kDynamicIneq)
+      {
+        checkDimensions(current_t, initial_variable);
+      }
       setVariable(initial_variable);
     }
     std::vector<double> x0(static_cast<size_t>(batch_) * StateDim);
@@ -274,11 +284,12 @@ public:
       }
       for(int i = 0; i < T; i++)
       {
-        for(int e = 0; e < InputDim; e++)
+        // (the leading u_list[i].size() / s_list[i].size() entries of the padded step; 0 beyond)
+        for(int e = 0; e < InputDim && e < v.u_list[i].size(); e++)
         {
           u[(static_cast<size_t>(b) * T + i) * InputDim + e] = v.u_list[i][e];
         }
-        for(int e = 0; e < IneqDim; e++)
+        for(int e = 0; e < IneqDim && e < v.s_list[i].size() && e < v.nu_list[i].size(); e++)
         {
           s[(static_cast<size_t>(b) * T + i) * IneqDim + e] = v.s_list[i][e];
           nu[(static_cast<size_t>(b) * T + i) * IneqDim + e] = v.nu_list[i][e];
@@ -297,6 +308,8 @@ public:
                         lambda = getField(NMPC_HIP_FMPC_FIELD_LAMBDA), s = getField(NMPC_HIP_FMPC_FIELD_S),
                         nu = getField(NMPC_HIP_FMPC_FIELD_NU);
     std::vector<Variable> out(batch_, Variable(T));
+    std::vector<int> m_dims, g_dims;
+    stepDims(m_dims, g_dims);
     for(int b = 0; b < batch_; b++)
     {
       for(int i = 0; i <= T; i++)
@@ -309,11 +322,15 @@ public:
       }
       for(int i = 0; i < T; i++)
       {
-        for(int e = 0; e < InputDim; e++)
+        const int m = m_dims[static_cast<size_t>(b) * T + i], g = g_dims[static_cast<size_t>(b) * T + i];
+        out[b].u_list[i].resize(m, 1);
+        out[b].s_list[i].resize(g, 1);
+        out[b].nu_list[i].resize(g, 1);
+        for(int e = 0; e < m; e++)
         {
           out[b].u_list[i][e] = u[(static_cast<size_t>(b) * T + i) * InputDim + e];
         }
-        for(int e = 0; e < IneqDim; e++)
+        for(int e = 0; e < g; e++)
         {
           out[b].s_list[i][e] = s[(static_cast<size_t>(b) * T + i) * IneqDim + e];
           out[b].nu_list[i][e] = nu[(static_cast<size_t>(b) * T + i) * IneqDim + e];
@@ -330,8 +347,11 @@ public:
     const int T = config_.horizon_steps;
     const std::vector<double> K = getField(NMPC_HIP_FMPC_FIELD_GAIN_K);
     std::vector<InputStateDimMatrix> out(batch_);
+    std::vector<int> m_dims, g_dims;
+    stepDims(m_dims, g_dims);
     for(int b = 0; b < batch_; b++)
     {
+      out[b].resize(m_dims[static_cast<size_t>(b) * T + step], StateDim); // (entries (a, c) at a + c InputDim on both sides)
       for(int e = 0; e < InputDim * StateDim; e++)
       {
         out[b].data()[e] = K[(static_cast<size_t>(b) * T + step) * InputDim * StateDim + e];
@@ -404,6 +424,51 @@ protected:
     throw std::runtime_error(msg);
   }
 
+  /** The per-step dimensions of the last solve, [B][T] (the capacities before the first solve). */
+  void stepDims(std::vector<int> & m_dims, std::vector<int> & g_dims) const
+  {
+    const size_t n = static_cast<size_t>(batch_) * config_.horizon_steps;
+    m_dims.assign(n, InputDim);
+    g_dims.assign(n, IneqDim);
+    if(nmpc_hip_fmpc_get_step_dims(handle_, m_dims.data(), g_dims.data(), 0) == NMPC_HIP_ERR_NOT_SOLVED)
+    {
+      m_dims.assign(n, InputDim);
+      g_dims.assign(n, IneqDim);
+    }
+  }
+
+  /** FmpcSolver::checkVariable's element-dimension test (FmpcSolver.hpp:314-344) for every instance. */
+  void checkDimensions(const std::vector<double> & current_t, const std::vector<Variable> & variable) const
+  {
+    for(int b = 0; b < batch_ && b < static_cast<int>(variable.size()); b++)
+    {
+      const Problem & p = own_problems_ ? problems_[b] : *problem_;
+      const Variable & v = variable[b];
+      for(int i = 0; i < config_.horizon_steps && i < static_cast<int>(v.u_list.size()) && i < static_cast<int>(v.s_list.size())
+                      && i < static_cast<int>(v.nu_list.size());
+          i++)
+      {
+        const double t = current_t[b] + i * p.dt();
+        const int input_dim = p.inputDim(t), ineq_dim = p.ineqDim(t);
+        if(v.u_list[i].size() != input_dim)
+        {
+          throw std::runtime_error("[FMPC] u_list[i] dimension should be " + std::to_string(input_dim) + " but "
+                                   + std::to_string(v.u_list[i].size()) + ". i: " + std::to_string(i) + ", time: " + std::to_string(t));
+        }
+        if(v.s_list[i].size() != ineq_dim)
+        {
+          throw std::runtime_error("[FMPC] s_list[i] dimension should be " + std::to_string(ineq_dim) + " but "
+                                   + std::to_string(v.s_list[i].size()) + ". i: " + std::to_string(i) + ", time: " + std::to_string(t));
+        }
+        if(v.nu_list[i].size() != ineq_dim)
+        {
+          throw std::runtime_error("[FMPC] nu_list[i] dimension should be " + std::to_string(ineq_dim) + " but "
+                                   + std::to_string(v.nu_list[i].size()) + ". i: " + std::to_string(i) + ", time: " + std::to_string(t));
+        }
+      }
+    }
+  }
+
   void checkLength(const char * name, size_t have, int want) const
   {
     if(static_cast<int>(have) != want)
@@ -458,5 +523,6 @@ protected:
   Configuration config_;
   nmpc_hip_fmpc_handle handle_ = nullptr;
   bool own_problems_ = false;
+  std::vector<Problem> problems_; // setProblems(): the per-instance objects (the dimension checks of solve())
 };
 } // namespace nmpc_amd

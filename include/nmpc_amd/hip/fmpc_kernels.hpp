@@ -431,6 +431,47 @@ __device__ __forceinline__ void loadVec(const double * base, const FmpcBuffers &
     out.data()[e] = base[at(buf, i, e, R * C, b)];
   }
 }
+
+/** Whether a problem type has a time-varying input or inequality dimension.  Its solves run the dims-aware kernels (the `_dims`
+    kernels below, FmpcOpsOf): they read the dimensions of every step from the solve's dims array [2][T][B] ints (input, then
+    inequality dimension), which fmpc_dims_kernel writes once when the solve begins, and touch the leading m(i) inputs and g(i)
+    rows of the capacity-sized arrays only.  The array is a kernel argument of its own, not a member of FmpcBuffers: appending a
+    member moves the hidden kernel arguments and every argument after the struct, which changes the code of every existing kernel. */
+template<class Problem>
+constexpr bool kStepDims = Problem::kDynamicInput || Problem::kDynamicIneq;
+
+struct StepDims
+{
+  int m, g;
+};
+
+/** m(i), g(i) of step i < T of instance b; for a fixed-dimension problem the capacities (compile-time constants: every guard
+    `a < d.m` / `j < d.g` folds away and dims is not read). */
+template<class Problem>
+__device__ __forceinline__ StepDims stepDims(const FmpcBuffers & buf, const int * dims, int i, int b)
+{
+  if constexpr(kStepDims<Problem>)
+  {
+    return {dims[static_cast<size_t>(i) * buf.B + b], dims[(static_cast<size_t>(buf.T) + i) * buf.B + b]};
+  }
+  else
+  {
+    (void)dims;
+    return {Problem::kInputDimMax, Problem::kIneqDim};
+  }
+}
+
+/** loadVec of the leading n entries into a vector of run-time size n; the entries beyond are set to 0 and not read. */
+template<int R, bool DR>
+__device__ __forceinline__ void loadVecN(const double * base, const FmpcBuffers & buf, int i, int b, Matrix<double, R, 1, DR, false> & out, int n)
+{
+  out.resize(n, 1);
+  NMPC_UNROLL
+  for(int e = 0; e < R; e++)
+  {
+    out.data()[e] = e < n ? base[at(buf, i, e, R, b)] : 0.0;
+  }
+}
 } // namespace fmpc
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -662,6 +703,159 @@ __global__ void fmpc_finish_kernel(FmpcBuffers buf)
   }
 }
 
+// ---- the problem-independent kernels of a problem with time-varying dimensions: the three above that loop over the inputs or
+// inequality rows, restricted to the leading m(i) / g(i) of every step (dims: [2][T][B], fmpc_dims_kernel).  Entries beyond a step's
+// dimensions are neither read nor written.
+
+/** fmpc_check_variable_kernel over the active rows: a negative s or nu beyond g(i) is not looked at (FmpcSolver.hpp:338-353 checks
+    s_list[i], nu_list[i] of size ineqDim(t)). */
+__global__ void fmpc_check_variable_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(tid >= static_cast<size_t>(buf.B) * buf.T)
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  const int g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+  bool negative = false;
+  double dot = 0;
+  for(int j = 0; j < g; j++)
+  {
+    const double sv = buf.s[fmpc::at(buf, i, j, buf.G, b)], nv = buf.nu[fmpc::at(buf, i, j, buf.G, b)];
+    negative = negative || sv < 0 || nv < 0;
+    dot += sv * nv;
+  }
+  buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
+  if(negative)
+  {
+    buf.status[b] = NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE;
+  }
+}
+
+/** fmpc_barrier_kernel with the mean of s . nu over the active rows: the sum divided by sum_i g(i) (FmpcSolver.hpp:370-392 sums the
+    per-step dot products and counts the rows of every s_list[i]).  No active row in the whole horizon: 0 / 0, as the reference. */
+__global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_dims_kernel(FmpcBuffers buf, const int * dims, int iter)
+{
+  __shared__ double sh[fmpc::kSlices][64];
+  __shared__ int shn[fmpc::kSlices][64];
+  const int lane = threadIdx.x & 63;
+  const int q = threadIdx.x >> 6;
+  const int b = blockIdx.x * 64 + lane;
+  const bool act = b < buf.B && buf.status[b] == fmpc::kStatusContinued;
+  double acc = 0;
+  int rows = 0;
+  if(act && buf.update_barrier_eps)
+  {
+    const int chunk = (buf.T + fmpc::kSlices - 1) / fmpc::kSlices;
+    const int i1 = min(buf.T, (q + 1) * chunk);
+    for(int i = q * chunk; i < i1; i++)
+    {
+      acc += buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)];
+      rows += dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+    }
+  }
+  sh[q][lane] = acc;
+  shn[q][lane] = rows;
+  syncThreadsFuzzed(__LINE__);
+  if(q == 0 && act)
+  {
+    double eps = buf.barrier_eps[b];
+    if(buf.update_barrier_eps)
+    {
+      double s_nu_ave = 0;
+      int n_rows = 0;
+      for(int k = 0; k < fmpc::kSlices; k++)
+      {
+        s_nu_ave += sh[k][lane];
+        n_rows += shn[k][lane];
+      }
+      s_nu_ave /= static_cast<double>(n_rows);
+      constexpr double sigma = 0.5;
+      constexpr double barrier_eps_min = 1e-8;
+      constexpr double barrier_eps_max = 1e6;
+      const double v = sigma * s_nu_ave;
+      eps = (v < barrier_eps_min) ? barrier_eps_min : ((barrier_eps_max < v) ? barrier_eps_max : v);
+      buf.barrier_eps[b] = eps;
+    }
+    buf.iters[b] = iter;
+    buf.flags[b] = 0;
+    double * row = buf.trace + (static_cast<size_t>(b) * buf.max_iter + (iter - 1)) * NMPC_HIP_FMPC_NTRACE;
+    row[NMPC_HIP_FMPC_TRACE_ITER] = iter;
+    row[NMPC_HIP_FMPC_TRACE_BARRIER_EPS] = eps;
+  }
+}
+
+/** fmpc_update_kernel over the leading m(i) inputs and g(i) rows of every step. */
+__global__ void fmpc_update_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  if(buf.status[b] != fmpc::kStatusContinued)
+  {
+    return;
+  }
+  const double alpha_s = buf.alpha[2 * buf.B + b];
+  const double alpha_nu = buf.alpha[1 * buf.B + b];
+  for(int e = 0; e < buf.N; e++)
+  {
+    const size_t k = fmpc::at(buf, i, e, buf.N, b);
+    buf.x[k] += alpha_s * buf.dx[k];
+    buf.lam[k] += alpha_nu * buf.dlam[k];
+  }
+  if(i < buf.T)
+  {
+    const int m = dims[static_cast<size_t>(i) * buf.B + b];
+    const int g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+    for(int e = 0; e < m; e++)
+    {
+      const size_t k = fmpc::at(buf, i, e, buf.M, b);
+      buf.u[k] += alpha_s * buf.du[k];
+    }
+    constexpr double min_positive_value = -DBL_MAX;
+    bool s_neg = false, nu_neg = false;
+    double dot = 0;
+    for(int e = 0; e < g; e++)
+    {
+      const size_t k = fmpc::at(buf, i, e, buf.G, b);
+      const double sv = buf.s[k] + alpha_s * buf.ds[k];
+      const double nv = buf.nu[k] + alpha_nu * buf.dnu[k];
+      buf.s[k] = sv;
+      buf.nu[k] = nv;
+      dot += sv * nv;
+      s_neg = s_neg || sv < 0;
+      nu_neg = nu_neg || nv < 0;
+    }
+    if(s_neg || nu_neg)
+    {
+      dot = 0;
+      for(int e = 0; e < g; e++)
+      {
+        const size_t k = fmpc::at(buf, i, e, buf.G, b);
+        double sv = buf.s[k], nv = buf.nu[k];
+        if(s_neg && sv < min_positive_value)
+        {
+          sv = min_positive_value;
+          buf.s[k] = sv;
+        }
+        if(nu_neg && nv < min_positive_value)
+        {
+          nv = min_positive_value;
+          buf.nu[k] = nv;
+        }
+        dot += sv * nv;
+      }
+    }
+    buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
+  }
+}
+
 /** Layout change between the C-ABI's arrays ([B][steps][E], the reference's per-instance std::vector of vectors) and the
     device arrays ([steps][E][B]): the transposition of a B x (steps E) matrix, through 32 x 32 tiles in LDS so that reads and writes
     are both whole lines (element by element one side of it touched a cache line per element: 20 us per field of the 4096 x T 200
@@ -698,7 +892,89 @@ __global__ void __launch_bounds__(256) fmpc_transpose_kernel(const double * src,
 // kernels instantiated per problem type
 // ---------------------------------------------------------------------------------------------------------------------
 
+/** Start of a solve of a problem with time-varying dimensions: m(i) = inputDim(t0 + i dt) and g(i) = ineqDim(t0 + i dt) of every
+    step into dims [2][T][B], once, so that every kernel of the solve sees the same dimensions.  A dimension outside [0, capacity]
+    is stored clamped and the instance gets NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE. */
+template<class Problem>
+__global__ void fmpc_dims_kernel(FmpcBuffers buf, int * dims)
+{
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(tid >= static_cast<size_t>(buf.B) * buf.T)
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
+  const double t = buf.t0[b] + i * prob.dt();
+  const int m = prob.inputDim(t), g = prob.ineqDim(t);
+  const int mc = m < 0 ? 0 : (m > Problem::kInputDimMax ? Problem::kInputDimMax : m);
+  const int gc = g < 0 ? 0 : (g > Problem::kIneqDim ? Problem::kIneqDim : g);
+  dims[static_cast<size_t>(i) * buf.B + b] = mc;
+  dims[(static_cast<size_t>(buf.T) + i) * buf.B + b] = gc;
+  if(mc != m || gc != g)
+  {
+    buf.status[b] = NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE;
+  }
+}
+
+namespace fmpc
+{
+/** init_complementary_variable (FmpcSolver.hpp:170-187) of one (instance, timestep); rows beyond g(i) are left as they are. */
+template<class Problem>
+__device__ __forceinline__ void initComplementary(const FmpcBuffers & buf, const int * dims)
+{
+  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(tid >= static_cast<size_t>(buf.B) * buf.T)
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  constexpr double initial_barrier_eps = 1e-4;
+  constexpr double complementary_variable_margin_rate = 1e-2;
+  constexpr double complementary_variable_min = 1e-2;
+  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
+  typename Problem::StateDimVector x;
+  typename Problem::InputDimVector u;
+  fmpc::loadVec(buf.x, buf, i, b, x);
+  const StepDims d = stepDims<Problem>(buf, dims, i, b);
+  if constexpr(kStepDims<Problem>)
+  {
+    loadVecN(buf.u, buf, i, b, u, d.m);
+  }
+  else
+  {
+    fmpc::loadVec(buf.u, buf, i, b, u);
+  }
+  const double t = buf.t0[b] + i * prob.dt();
+  const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
+  NMPC_UNROLL
+  for(int j = 0; j < G; j++)
+  {
+    if(j < d.g)
+    {
+      const double neg_g = -1 * g[j];
+      const double sj = (1.0 + complementary_variable_margin_rate) * (neg_g < complementary_variable_min ? complementary_variable_min : neg_g);
+      const double r = initial_barrier_eps * (1.0 / sj);
+      buf.s[fmpc::at(buf, i, j, G, b)] = sj;
+      buf.nu[fmpc::at(buf, i, j, G, b)] =
+          (1.0 + complementary_variable_margin_rate) * (r < complementary_variable_min ? complementary_variable_min : r);
+    }
+  }
+  if(i == 0)
+  {
+    buf.barrier_eps[b] = initial_barrier_eps;
+  }
+  (void)N;
+  (void)M;
+}
+} // namespace fmpc
+
 /** init_complementary_variable (FmpcSolver.hpp:170-187). */
+// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
+// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void fmpc_init_complementary_kernel(FmpcBuffers buf)
 {
@@ -737,6 +1013,11 @@ __global__ void fmpc_init_complementary_kernel(FmpcBuffers buf)
   (void)N;
   (void)M;
 }
+template<class Problem>
+__global__ void fmpc_init_complementary_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  fmpc::initComplementary<Problem>(buf, dims);
+}
 
 /** Step 1 of procOnce (FmpcSolver.hpp:394-441) for one (instance, timestep), fused with the pre-process of the backward pass
     (:562-574: everything of it that does not depend on P) and with this timestep's terms of calcKktError (:493-520). */
@@ -767,35 +1048,53 @@ struct CoefInputs
   typename Problem::IneqDimVector s, nu;
 };
 template<class Problem>
-__device__ __forceinline__ void loadCoefInputs(const FmpcBuffers & buf, int b, int i, CoefInputs<Problem> & in)
+__device__ __forceinline__ void loadCoefInputs(const FmpcBuffers & buf, int b, int i, CoefInputs<Problem> & in, const int * dims = nullptr)
 {
   loadVec(buf.x, buf, i, b, in.x);
   loadVec(buf.lam, buf, i, b, in.lambda);
   if(i < buf.T)
   {
-    loadVec(buf.u, buf, i, b, in.u);
+    if constexpr(kStepDims<Problem>)
+    {
+      const StepDims d = stepDims<Problem>(buf, dims, i, b);
+      loadVecN(buf.u, buf, i, b, in.u, d.m);
+      loadVecN(buf.s, buf, i, b, in.s, d.g);
+      loadVecN(buf.nu, buf, i, b, in.nu, d.g);
+    }
+    else
+    {
+      (void)dims;
+      loadVec(buf.u, buf, i, b, in.u);
+    }
     loadVec(buf.x, buf, i + 1, b, in.next_x);
     loadVec(buf.lam, buf, i + 1, b, in.next_lambda);
-    loadVec(buf.s, buf, i, b, in.s);
-    loadVec(buf.nu, buf, i, b, in.nu);
+    if constexpr(!kStepDims<Problem>)
+    {
+      loadVec(buf.s, buf, i, b, in.s);
+      loadVec(buf.nu, buf, i, b, in.nu);
+    }
   }
 }
 /** \tparam kPart 0: whatever timestep i is; 1: i is the terminal timestep (i == buf.T); 2: i is not — a caller that knows which
     (fmpc_tail_kernel) leaves the other branch out of its code */
 template<class Problem, class Sink, int kPart = 0>
 __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, int i, const CoefInputs<Problem> & in, Sink & sink,
-                                               const Problem & prob, double t0);
+                                               const Problem & prob, double t0, const int * dims = nullptr);
 template<class Problem, class Sink, int kPart = 0>
-__device__ __forceinline__ void coefficients(const FmpcBuffers & buf, int b, int i, const CoefInputs<Problem> & in, Sink & sink)
+__device__ __forceinline__ void coefficients(const FmpcBuffers & buf, int b, int i, const CoefInputs<Problem> & in, Sink & sink,
+                                             const int * dims = nullptr)
 {
   const Problem prob = loadProblem<Problem>(buf, b);
-  coefficientsOf<Problem, Sink, kPart>(buf, b, i, in, sink, prob, buf.t0[b]);
+  coefficientsOf<Problem, Sink, kPart>(buf, b, i, in, sink, prob, buf.t0[b], dims);
 }
 /** coefficients() with the instance's problem object and current_t handed in (fmpc_tail_kernel keeps them at hand: a load from
     global memory in the middle of its walk waits for everything requested before it). */
+/** With time-varying dimensions (dims, kStepDims) only the leading m(i) inputs and g(i) rows enter any sum, the model sees
+    arguments of those sizes, and the record's input entries beyond m(i) are written as exactly 0: the Riccati recursion then
+    computes on the m(i) x m(i) block of G alone (Ldlt's pivot rule never picks an all-zero trailing row). */
 template<class Problem, class Sink, int kPart>
 __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, int i, const CoefInputs<Problem> & in, Sink & sink,
-                                               const Problem & prob, double t0)
+                                               const Problem & prob, double t0, const int * dims)
 {
   constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
   using CL = CoefLayout<N, M>;
@@ -840,6 +1139,7 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   const typename Problem::StateDimVector & next_x = in.next_x, & next_lambda = in.next_lambda;
   const typename Problem::IneqDimVector & s = in.s, & nu = in.nu;
 
+  const StepDims d = stepDims<Problem>(buf, dims, i, b);
   typename Problem::StateStateDimMatrix A, Lxx;
   typename Problem::StateInputDimMatrix Bm, Lxu;
   typename Problem::IneqStateDimMatrix C;
@@ -847,6 +1147,15 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   typename Problem::StateDimVector Lx;
   typename Problem::InputDimVector Lu;
   typename Problem::InputInputDimMatrix Luu;
+  if constexpr(kStepDims<Problem>)
+  {
+    Bm.resize(N, d.m);
+    Lxu.resize(N, d.m);
+    C.resize(d.g, N);
+    D.resize(d.g, d.m);
+    Lu.resize(d.m, 1);
+    Luu.resize(d.m, d.m);
+  }
   prob.calcStateEqDeriv(t, x, u, A, Bm);
   prob.calcIneqConstDeriv(t, x, u, C, D);
   prob.calcRunningCostDeriv(t, x, u, Lx, Lu, Lxx, Luu, Lxu);
@@ -876,8 +1185,11 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   NMPC_UNROLL
   for(int a = 0; a < G; a++)
   {
-    g_bar[a] = g[a] + s[a]; // (2.23d)
-    part = fused(g_bar[a], g_bar[a], part);
+    g_bar[a] = a < d.g ? g[a] + s[a] : 0.0; // (2.23d)
+    if(a < d.g)
+    {
+      part = fused(g_bar[a], g_bar[a], part);
+    }
     nan_acc.add(g_bar[a]);
   }
   kkt += part;
@@ -894,7 +1206,10 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
     NMPC_UNROLL
     for(int r = 0; r < G; r++)
     {
-      ct = fused(C(r, a), nu[r], ct);
+      if(r < d.g)
+      {
+        ct = fused(C(r, a), nu[r], ct);
+      }
     }
     Lx_bar[a] = ((-1 * lambda[a] + dt * Lx[a]) + at) + ct;
     part = fused(Lx_bar[a], Lx_bar[a], part);
@@ -906,30 +1221,43 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   NMPC_UNROLL
   for(int a = 0; a < M; a++) // (2.25c)
   {
-    double bt = 0, dn = 0;
-    NMPC_UNROLL
-    for(int r = 0; r < N; r++)
+    if(a < d.m)
     {
-      bt = fused(Bm(r, a), next_lambda[r], bt);
+      double bt = 0, dn = 0;
+      NMPC_UNROLL
+      for(int r = 0; r < N; r++)
+      {
+        bt = fused(Bm(r, a), next_lambda[r], bt);
+      }
+      NMPC_UNROLL
+      for(int r = 0; r < G; r++)
+      {
+        if(r < d.g)
+        {
+          dn = fused(D(r, a), nu[r], dn);
+        }
+      }
+      Lu_bar[a] = (dt * Lu[a] + bt) + dn;
+      part = fused(Lu_bar[a], Lu_bar[a], part);
     }
-    NMPC_UNROLL
-    for(int r = 0; r < G; r++)
+    else
     {
-      dn = fused(D(r, a), nu[r], dn);
+      Lu_bar[a] = 0.0;
     }
-    Lu_bar[a] = (dt * Lu[a] + bt) + dn;
-    part = fused(Lu_bar[a], Lu_bar[a], part);
     nan_acc.add(Lu_bar[a]);
-    nan_acc.add(Lu[a]);
+    nan_acc.add(a < d.m ? Lu[a] : 0.0);
   }
   kkt += part;
   part = 0;
   NMPC_UNROLL
   for(int j = 0; j < G; j++) // complementarity term of calcKktError(0.0) (:509-510)
   {
-    const double v = s[j] * nu[j];
-    const double e = v < 0.0 ? 0.0 : v; // array().max(0): (a < 0) ? 0 : a
-    part = fused(e, e, part);
+    if(j < d.g)
+    {
+      const double v = s[j] * nu[j];
+      const double e = v < 0.0 ? 0.0 : v; // array().max(0): (a < 0) ? 0 : a
+      part = fused(e, e, part);
+    }
   }
   kkt += part;
   sink.kkt(kkt);
@@ -944,23 +1272,23 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   NMPC_UNROLL
   for(int e = 0; e < N * M; e++)
   {
-    nan_acc.add(Bm.data()[e]);
-    nan_acc.add(Lxu.data()[e]);
+    nan_acc.add(e / N < d.m ? Bm.data()[e] : 0.0);
+    nan_acc.add(e / N < d.m ? Lxu.data()[e] : 0.0);
   }
   NMPC_UNROLL
   for(int e = 0; e < G * N; e++)
   {
-    nan_acc.add(C.data()[e]);
+    nan_acc.add(e % G < d.g ? C.data()[e] : 0.0);
   }
   NMPC_UNROLL
   for(int e = 0; e < G * M; e++)
   {
-    nan_acc.add(D.data()[e]);
+    nan_acc.add(e % G < d.g && e / G < d.m ? D.data()[e] : 0.0);
   }
   NMPC_UNROLL
   for(int e = 0; e < M * M; e++)
   {
-    nan_acc.add(Luu.data()[e]);
+    nan_acc.add(e % M < d.m && e / M < d.m ? Luu.data()[e] : 0.0);
   }
   if(nan || nan_acc.any())
   {
@@ -974,8 +1302,16 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   NMPC_UNROLL
   for(int j = 0; j < G; j++)
   {
-    nu_s[j] = nu[j] / s[j];
-    tilde_sub[j] = (nu_s[j] * g_bar[j] - nu[j]) + barrier_eps * (1.0 / s[j]);
+    if(j < d.g)
+    {
+      nu_s[j] = nu[j] / s[j];
+      tilde_sub[j] = (nu_s[j] * g_bar[j] - nu[j]) + barrier_eps * (1.0 / s[j]);
+    }
+    else
+    {
+      nu_s[j] = 0.0;
+      tilde_sub[j] = 0.0;
+    }
   }
   NMPC_UNROLL
   for(int e = 0; e < N * N; e++)
@@ -985,7 +1321,7 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
   NMPC_UNROLL
   for(int e = 0; e < N * M; e++)
   {
-    sink.coef(CL::B + e, Bm.data()[e]);
+    sink.coef(CL::B + e, e / N < d.m ? Bm.data()[e] : 0.0);
   }
   NMPC_UNROLL
   for(int a = 0; a < N; a++)
@@ -1002,7 +1338,10 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
       NMPC_UNROLL
       for(int j = 0; j < G; j++)
       {
-        acc += (C(j, a) * nu_s[j]) * C(j, c);
+        if(j < d.g)
+        {
+          acc += (C(j, a) * nu_s[j]) * C(j, c);
+        }
       }
       sink.coef(CL::QXX + a + c * N, dt * Lxx(a, c) + acc); // (2.28c)
     }
@@ -1017,9 +1356,12 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
       NMPC_UNROLL
       for(int j = 0; j < G; j++)
       {
-        acc += (D(j, a) * nu_s[j]) * D(j, c);
+        if(j < d.g)
+        {
+          acc += (D(j, a) * nu_s[j]) * D(j, c);
+        }
       }
-      sink.coef(CL::QUU + a + c * M, dt * Luu(a, c) + acc); // (2.28e)
+      sink.coef(CL::QUU + a + c * M, (a < d.m && c < d.m) ? dt * Luu(a, c) + acc : 0.0); // (2.28e)
     }
     NMPC_UNROLL
     for(int a = 0; a < N; a++)
@@ -1028,9 +1370,12 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
       NMPC_UNROLL
       for(int j = 0; j < G; j++)
       {
-        acc += (C(j, a) * nu_s[j]) * D(j, c);
+        if(j < d.g)
+        {
+          acc += (C(j, a) * nu_s[j]) * D(j, c);
+        }
       }
-      sink.coef(CL::QXU + a + c * N, dt * Lxu(a, c) + acc); // (2.28d)
+      sink.coef(CL::QXU + a + c * N, c < d.m ? dt * Lxu(a, c) + acc : 0.0); // (2.28d)
     }
   }
   NMPC_UNROLL
@@ -1040,7 +1385,10 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
     NMPC_UNROLL
     for(int j = 0; j < G; j++)
     {
-      acc += C(j, a) * tilde_sub[j];
+      if(j < d.g)
+      {
+        acc += C(j, a) * tilde_sub[j];
+      }
     }
     sink.coef(CL::LXT + a, Lx_bar[a] + acc); // (2.28f)
   }
@@ -1051,9 +1399,12 @@ __device__ __forceinline__ void coefficientsOf(const FmpcBuffers & buf, int b, i
     NMPC_UNROLL
     for(int j = 0; j < G; j++)
     {
-      acc += D(j, a) * tilde_sub[j];
+      if(j < d.g)
+      {
+        acc += D(j, a) * tilde_sub[j];
+      }
     }
-    sink.coef(CL::LUT + a, Lu_bar[a] + acc); // (2.28g)
+    sink.coef(CL::LUT + a, a < d.m ? Lu_bar[a] + acc : 0.0); // (2.28g)
   }
 }
 
@@ -1108,6 +1459,28 @@ __global__ void __launch_bounds__(256) fmpc_coeff_kernel(FmpcBuffers buf)
   fmpc::CoefInputs<Problem> in;
   fmpc::loadCoefInputs<Problem>(buf, b, i, in);
   fmpc::coefficients<Problem>(buf, b, i, in, sink);
+}
+
+/** fmpc_coeff_kernel of a problem with time-varying dimensions (dims: fmpc_dims_kernel). */
+template<class Problem>
+__global__ void __launch_bounds__(256) fmpc_coeff_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax;
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  if(buf.status[b] != fmpc::kStatusContinued)
+  {
+    return;
+  }
+  fmpc::GlobalCoefSink<N, M, true> sink{buf, b, i};
+  fmpc::CoefInputs<Problem> in;
+  fmpc::loadCoefInputs<Problem>(buf, b, i, in, dims);
+  fmpc::coefficients<Problem>(buf, b, i, in, sink, dims);
 }
 
 namespace fmpc
@@ -3107,6 +3480,142 @@ __global__ void __launch_bounds__(384) fmpc_riccati_fused_kernel(FmpcBuffers buf
     per-timestep candidates of the fraction-to-boundary rule (:713-731).  C, D and g are re-evaluated instead of being kept
     from the coefficient kernel (for the box-type rows of the reference's problems that is a handful of instructions against
     (G N + G M + G) x 16 bytes of HBM traffic per timestep). */
+namespace fmpc
+{
+template<class Problem>
+__device__ __forceinline__ void delta(const FmpcBuffers & buf, const int * dims)
+{
+  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
+  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  using GL = fmpc::GainLayout<N, M>;
+  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
+  {
+    return;
+  }
+  const int b = static_cast<int>(tid % buf.B);
+  const int i = static_cast<int>(tid / buf.B);
+  if(buf.status[b] != fmpc::kStatusContinued)
+  {
+    return;
+  }
+  typename Problem::StateDimVector x, dx;
+  fmpc::loadVec(buf.dx, buf, i, b, dx);
+  bool nan = false;
+  NMPC_UNROLL
+  for(int a = 0; a < N; a++) // (2.33)
+  {
+    double acc = 0;
+    NMPC_UNROLL
+    for(int r = 0; r < N; r++)
+    {
+      acc += buf.gain[fmpc::at(buf, i, GL::P + a + r * N, GL::kStride, b)] * dx[r];
+    }
+    const double dl = acc - buf.gain[fmpc::at(buf, i, GL::S + a, GL::kStride, b)];
+    buf.dlam[fmpc::at(buf, i, a, N, b)] = dl;
+    nan = nan || fmpc::bad(dl) || fmpc::bad(dx[a]);
+  }
+  if(i == buf.T)
+  {
+    if(nan)
+    {
+      atomicOr(&buf.flags[b], 2);
+    }
+    return;
+  }
+  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
+  const double t = buf.t0[b] + i * prob.dt();
+  typename Problem::InputDimVector u, du;
+  typename Problem::IneqDimVector s, nu;
+  const StepDims d = stepDims<Problem>(buf, dims, i, b);
+  fmpc::loadVec(buf.x, buf, i, b, x);
+  if constexpr(kStepDims<Problem>)
+  {
+    loadVecN(buf.u, buf, i, b, u, d.m);
+    loadVecN(buf.du, buf, i, b, du, d.m);
+  }
+  else
+  {
+    fmpc::loadVec(buf.u, buf, i, b, u);
+    fmpc::loadVec(buf.du, buf, i, b, du);
+  }
+  NMPC_UNROLL
+  for(int a = 0; a < M; a++)
+  {
+    nan = nan || fmpc::bad(du[a]);
+  }
+  if constexpr(kStepDims<Problem>)
+  {
+    loadVecN(buf.s, buf, i, b, s, d.g);
+    loadVecN(buf.nu, buf, i, b, nu, d.g);
+  }
+  else
+  {
+    fmpc::loadVec(buf.s, buf, i, b, s);
+    fmpc::loadVec(buf.nu, buf, i, b, nu);
+  }
+  typename Problem::IneqStateDimMatrix C;
+  typename Problem::IneqInputDimMatrix D;
+  if constexpr(kStepDims<Problem>)
+  {
+    C.resize(d.g, N);
+    D.resize(d.g, d.m);
+  }
+  prob.calcIneqConstDeriv(t, x, u, C, D);
+  const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
+  const double barrier_eps = buf.barrier_eps[b];
+  constexpr double margin_ratio = 0.995;
+  double alpha_s = 1.0, alpha_nu = 1.0;
+  NMPC_UNROLL
+  for(int j = 0; j < G; j++)
+  {
+    if(j >= d.g)
+    {
+      buf.ds[fmpc::at(buf, i, j, G, b)] = 0.0; // (beyond the step's dimension: exactly 0)
+      buf.dnu[fmpc::at(buf, i, j, G, b)] = 0.0;
+      continue;
+    }
+    double cx = 0, dd = 0;
+    NMPC_UNROLL
+    for(int r = 0; r < N; r++)
+    {
+      cx += C(j, r) * dx[r];
+    }
+    NMPC_UNROLL
+    for(int r = 0; r < M; r++)
+    {
+      if(r < d.m)
+      {
+        dd += D(j, r) * du[r];
+      }
+    }
+    const double g_bar = g[j] + s[j];
+    const double dsj = -1 * ((cx + dd) + g_bar); // (2.27a)
+    const double dnj = -1 * (nu[j] * (dsj + s[j]) - barrier_eps) / s[j]; // (2.27b)
+    buf.ds[fmpc::at(buf, i, j, G, b)] = dsj;
+    buf.dnu[fmpc::at(buf, i, j, G, b)] = dnj;
+    nan = nan || fmpc::bad(dsj) || fmpc::bad(dnj);
+    if(dsj < 0) // (19.9) in Nocedal & Wright
+    {
+      const double c = -1 * margin_ratio * s[j] / dsj;
+      alpha_s = (c < alpha_s) ? c : alpha_s;
+    }
+    if(dnj < 0)
+    {
+      const double c = -1 * margin_ratio * nu[j] / dnj;
+      alpha_nu = (c < alpha_nu) ? c : alpha_nu;
+    }
+  }
+  buf.part[fmpc::at(buf, i, 1, fmpc::kPartSlots, b)] = alpha_s;
+  buf.part[fmpc::at(buf, i, 2, fmpc::kPartSlots, b)] = alpha_nu;
+  if(nan)
+  {
+    atomicOr(&buf.flags[b], 2);
+  }
+}
+} // namespace fmpc
+
+// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
+// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void __launch_bounds__(256) fmpc_delta_kernel(FmpcBuffers buf)
 {
@@ -3206,6 +3715,12 @@ __global__ void __launch_bounds__(256) fmpc_delta_kernel(FmpcBuffers buf)
     atomicOr(&buf.flags[b], 2);
   }
 }
+/** fmpc_delta_kernel of a problem with time-varying dimensions: rows beyond g(i) get ds = dnu = 0 and no step-length candidate. */
+template<class Problem>
+__global__ void __launch_bounds__(256) fmpc_delta_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  fmpc::delta<Problem>(buf, dims);
+}
 
 /** l1NormDirectionalDeriv (MathUtils.h:17-38) for one row: func_i, (jac row i) . dir. */
 __device__ __forceinline__ double fmpcL1RowDeriv(double func_i, double row_dot_dir)
@@ -3216,6 +3731,304 @@ __device__ __forceinline__ double fmpcL1RowDeriv(double func_i, double row_dot_d
 /** Line search on the l1 merit function (FmpcSolver.hpp:748-792 with setupMeritFunc :840-936 and calcMeritFunc :938-981), one
     instance per lane.  Off by default in the reference (FmpcSolver.h:85) and in both of its tests; kept sequential over the
     horizon because the number of backtracking trials differs per instance. */
+namespace fmpc
+{
+template<class Problem>
+__device__ __forceinline__ void lineSearch(const FmpcBuffers & buf, int iter, const int * dims)
+{
+  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
+  using CL = fmpc::CoefLayout<N, M>;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if(b >= buf.B || buf.status[b] != fmpc::kStatusContinued)
+  {
+    return;
+  }
+  const int T = buf.T;
+  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
+  const double dt = prob.dt();
+  const double t0 = buf.t0[b];
+  const double barrier_eps = buf.barrier_eps[b];
+
+  // merit function at a trial step length: FmpcSolver::calcMeritFunc on variable_ + alpha * delta_variable_ (alpha = 0: the
+  // function part of setupMeritFunc)
+  auto merit = [&](double alpha, double & obj, double & con) {
+    obj = 0;
+    con = 0;
+    typename Problem::StateDimVector x, next_x;
+    NMPC_UNROLL
+    for(int a = 0; a < N; a++)
+    {
+      x[a] = buf.x[fmpc::at(buf, 0, a, N, b)] + alpha * buf.dx[fmpc::at(buf, 0, a, N, b)];
+      con += fabs(buf.x0[static_cast<size_t>(a) * buf.B + b] - x[a]);
+    }
+    for(int i = 0; i < T; i++)
+    {
+      const double t = t0 + i * dt;
+      const fmpc::StepDims d = fmpc::stepDims<Problem>(buf, dims, i, b);
+      typename Problem::InputDimVector u;
+      if constexpr(fmpc::kStepDims<Problem>)
+      {
+        u.resize(d.m, 1);
+      }
+      NMPC_UNROLL
+      for(int a = 0; a < M; a++)
+      {
+        u[a] = a < d.m ? buf.u[fmpc::at(buf, i, a, M, b)] + alpha * buf.du[fmpc::at(buf, i, a, M, b)] : 0.0;
+      }
+      NMPC_UNROLL
+      for(int a = 0; a < N; a++)
+      {
+        next_x[a] = buf.x[fmpc::at(buf, i + 1, a, N, b)] + alpha * buf.dx[fmpc::at(buf, i + 1, a, N, b)];
+      }
+      obj += prob.runningCost(t, x, u) * dt;
+      const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
+      double logsum = 0, c2 = 0;
+      NMPC_UNROLL
+      for(int j = 0; j < G; j++)
+      {
+        if(j < d.g)
+        {
+          const double sj = buf.s[fmpc::at(buf, i, j, G, b)] + alpha * buf.ds[fmpc::at(buf, i, j, G, b)];
+          logsum += log(sj);
+          c2 += fabs(g[j] + sj);
+        }
+      }
+      obj += -1 * barrier_eps * logsum;
+      const typename Problem::StateDimVector f = prob.stateEq(t, x, u);
+      double c1 = 0;
+      NMPC_UNROLL
+      for(int a = 0; a < N; a++)
+      {
+        c1 += fabs(f[a] - next_x[a]);
+      }
+      con += c1;
+      con += c2;
+      x = next_x;
+    }
+    obj += prob.terminalCost(t0 + T * dt, x);
+  };
+
+  // setupMeritFunc: directional derivatives (:852-905)
+  double merit_func_obj, merit_func_const;
+  merit(0.0, merit_func_obj, merit_func_const);
+  double merit_deriv_obj = 0, merit_deriv_const = 0;
+  {
+    double acc = 0;
+    NMPC_UNROLL
+    for(int a = 0; a < N; a++)
+    {
+      const double cf = buf.x0[static_cast<size_t>(a) * buf.B + b] - buf.x[fmpc::at(buf, 0, a, N, b)];
+      acc += fmpcL1RowDeriv(cf, -1 * buf.dx[fmpc::at(buf, 0, a, N, b)]);
+    }
+    merit_deriv_const += acc;
+  }
+  for(int i = 0; i < T; i++)
+  {
+    const double t = t0 + i * dt;
+    typename Problem::StateDimVector x, next_x, dx, dnx;
+    typename Problem::InputDimVector u, du;
+    typename Problem::IneqDimVector s, ds;
+    const fmpc::StepDims d = fmpc::stepDims<Problem>(buf, dims, i, b);
+    fmpc::loadVec(buf.x, buf, i, b, x);
+    fmpc::loadVec(buf.x, buf, i + 1, b, next_x);
+    fmpc::loadVec(buf.dx, buf, i, b, dx);
+    fmpc::loadVec(buf.dx, buf, i + 1, b, dnx);
+    if constexpr(fmpc::kStepDims<Problem>)
+    {
+      fmpc::loadVecN(buf.u, buf, i, b, u, d.m);
+      fmpc::loadVecN(buf.du, buf, i, b, du, d.m);
+      fmpc::loadVecN(buf.s, buf, i, b, s, d.g);
+      fmpc::loadVecN(buf.ds, buf, i, b, ds, d.g);
+    }
+    else
+    {
+      fmpc::loadVec(buf.u, buf, i, b, u);
+      fmpc::loadVec(buf.du, buf, i, b, du);
+      fmpc::loadVec(buf.s, buf, i, b, s);
+      fmpc::loadVec(buf.ds, buf, i, b, ds);
+    }
+    typename Problem::StateDimVector Lx;
+    typename Problem::InputDimVector Lu;
+    typename Problem::StateStateDimMatrix Lxx;
+    typename Problem::InputInputDimMatrix Luu;
+    typename Problem::StateInputDimMatrix Lxu;
+    if constexpr(fmpc::kStepDims<Problem>)
+    {
+      Lu.resize(d.m, 1);
+      Luu.resize(d.m, d.m);
+      Lxu.resize(N, d.m);
+    }
+    prob.calcRunningCostDeriv(t, x, u, Lx, Lu, Lxx, Luu, Lxu);
+    double lx = 0, lu = 0, invdot = 0;
+    NMPC_UNROLL
+    for(int a = 0; a < N; a++)
+    {
+      lx += Lx[a] * dx[a];
+    }
+    NMPC_UNROLL
+    for(int a = 0; a < M; a++)
+    {
+      if(a < d.m)
+      {
+        lu += Lu[a] * du[a];
+      }
+    }
+    merit_deriv_obj += (lx + lu) * dt;
+    NMPC_UNROLL
+    for(int j = 0; j < G; j++)
+    {
+      if(j < d.g)
+      {
+        invdot += (1.0 / s[j]) * ds[j];
+      }
+    }
+    merit_deriv_obj += -1 * barrier_eps * invdot;
+    {
+      const typename Problem::StateDimVector f = prob.stateEq(t, x, u);
+      double dA = 0, dB = 0, dI = 0;
+      NMPC_UNROLL
+      for(int a = 0; a < N; a++)
+      {
+        const double cf = f[a] - next_x[a];
+        double ra = 0, rb = 0;
+        NMPC_UNROLL
+        for(int r = 0; r < N; r++)
+        {
+          ra += buf.coef[fmpc::at(buf, i, CL::A + a + r * N, CL::kStride, b)] * dx[r];
+        }
+        NMPC_UNROLL
+        for(int r = 0; r < M; r++)
+        {
+          if(r < d.m)
+          {
+            rb += buf.coef[fmpc::at(buf, i, CL::B + a + r * N, CL::kStride, b)] * du[r];
+          }
+        }
+        dA += fmpcL1RowDeriv(cf, ra);
+        dB += fmpcL1RowDeriv(cf, rb);
+        dI += fmpcL1RowDeriv(cf, -1 * dnx[a]);
+      }
+      merit_deriv_const += dA;
+      merit_deriv_const += dB;
+      merit_deriv_const += dI;
+    }
+    {
+      typename Problem::IneqStateDimMatrix C;
+      typename Problem::IneqInputDimMatrix D;
+      if constexpr(fmpc::kStepDims<Problem>)
+      {
+        C.resize(d.g, N);
+        D.resize(d.g, d.m);
+      }
+      prob.calcIneqConstDeriv(t, x, u, C, D);
+      const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
+      double dC = 0, dD = 0, dI = 0;
+      NMPC_UNROLL
+      for(int j = 0; j < G; j++)
+      {
+        if(j >= d.g)
+        {
+          continue;
+        }
+        const double cf = g[j] + s[j];
+        double rc = 0, rd = 0;
+        NMPC_UNROLL
+        for(int r = 0; r < N; r++)
+        {
+          rc += C(j, r) * dx[r];
+        }
+        NMPC_UNROLL
+        for(int r = 0; r < M; r++)
+        {
+          if(r < d.m)
+          {
+            rd += D(j, r) * du[r];
+          }
+        }
+        dC += fmpcL1RowDeriv(cf, rc);
+        dD += fmpcL1RowDeriv(cf, rd);
+        dI += fmpcL1RowDeriv(cf, ds[j]);
+      }
+      merit_deriv_const += dC;
+      merit_deriv_const += dD;
+      merit_deriv_const += dI;
+    }
+  }
+  {
+    typename Problem::StateDimVector xT, Vx;
+    typename Problem::StateStateDimMatrix Vxx;
+    fmpc::loadVec(buf.x, buf, T, b, xT);
+    prob.calcTerminalCostDeriv(t0 + T * dt, xT, Vx, Vxx);
+    double acc = 0;
+    NMPC_UNROLL
+    for(int a = 0; a < N; a++)
+    {
+      acc += Vx[a] * buf.dx[fmpc::at(buf, T, a, N, b)];
+    }
+    merit_deriv_obj += acc;
+  }
+
+  constexpr double merit_const_scale_min = 1e-3;
+  double merit_const_scale;
+  if(buf.merit_const_scale_from_lagrange_multipliers) // (18.32) in Nocedal & Wright
+  {
+    merit_const_scale = merit_const_scale_min;
+    for(int i = 0; i <= T; i++)
+    {
+      for(int a = 0; a < N; a++)
+      {
+        const double v = fabs(buf.lam[fmpc::at(buf, i, a, N, b)]);
+        merit_const_scale = (merit_const_scale < v) ? v : merit_const_scale;
+      }
+      if(i < T)
+      {
+        const int g_i = fmpc::stepDims<Problem>(buf, dims, i, b).g;
+        for(int j = 0; j < g_i; j++)
+        {
+          const double v = fabs(buf.nu[fmpc::at(buf, i, j, G, b)]);
+          merit_const_scale = (merit_const_scale < v) ? v : merit_const_scale;
+        }
+      }
+    }
+  }
+  else // (18.33)
+  {
+    constexpr double rho = 0.5;
+    const double v = merit_deriv_obj / ((1.0 - rho) * merit_func_const);
+    merit_const_scale = (v < merit_const_scale_min) ? merit_const_scale_min : v; // std::max(v, min)
+  }
+  const double merit_func = merit_func_obj + merit_const_scale * merit_func_const;
+  const double merit_deriv = merit_deriv_obj + merit_const_scale * merit_deriv_const;
+  buf.merit[0 * buf.B + b] = merit_func;
+  buf.merit[1 * buf.B + b] = merit_deriv;
+  buf.merit[2 * buf.B + b] = merit_const_scale;
+
+  constexpr double armijo_scale = 1e-3;
+  constexpr double alpha_s_update_ratio = 0.5;
+  constexpr double alpha_s_min = 1e-10;
+  double alpha_s = buf.alpha[0 * buf.B + b];
+  while(true)
+  {
+    if(alpha_s < alpha_s_min)
+    {
+      break;
+    }
+    double obj, con;
+    merit(alpha_s, obj, con);
+    const double merit_func_new = obj + merit_const_scale * con;
+    if(merit_func_new < merit_func + armijo_scale * alpha_s * merit_deriv)
+    {
+      break;
+    }
+    alpha_s *= alpha_s_update_ratio;
+  }
+  buf.alpha[2 * buf.B + b] = alpha_s;
+  buf.trace[(static_cast<size_t>(b) * buf.max_iter + (iter - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_ALPHA_S] = alpha_s;
+}
+} // namespace fmpc
+
+// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
+// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void __launch_bounds__(64) fmpc_line_search_kernel(FmpcBuffers buf, int iter)
 {
@@ -3461,10 +4274,83 @@ __global__ void __launch_bounds__(64) fmpc_line_search_kernel(FmpcBuffers buf, i
   buf.alpha[2 * buf.B + b] = alpha_s;
   buf.trace[(static_cast<size_t>(b) * buf.max_iter + (iter - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_ALPHA_S] = alpha_s;
 }
+/** fmpc_line_search_kernel of a problem with time-varying dimensions: every sum over the leading m(i) inputs / g(i) rows. */
+template<class Problem>
+__global__ void __launch_bounds__(64) fmpc_line_search_dims_kernel(FmpcBuffers buf, const int * dims, int iter)
+{
+  fmpc::lineSearch<Problem>(buf, iter, dims);
+}
 
 /** The plant step of the reference's closed-loop tests (TestFmpcOscillator.cpp:191, TestFmpcCartPole.cpp:352):
     x <- stateEq(t, x, u + K_0 (x_list[0] - x) * use_feedback, sim_dt), t += sim_dt, `substeps` times, on the handle's resident
     arrays; u = u_list[0] of the last solve.  x_plant / t_plant: [N][B] / [B]. */
+namespace fmpc
+{
+template<class Problem>
+__device__ __forceinline__ void plant(const FmpcBuffers & buf, double * x_plant, double * t_plant, double sim_dt, int substeps, int use_feedback,
+                                      const int * dims)
+{
+  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax;
+  using GL = fmpc::GainLayout<N, M>;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if(b >= buf.B)
+  {
+    return;
+  }
+  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
+  typename Problem::StateDimVector x;
+  typename Problem::InputDimVector u0;
+  NMPC_UNROLL
+  for(int a = 0; a < N; a++)
+  {
+    x[a] = x_plant[static_cast<size_t>(a) * buf.B + b];
+  }
+  // u_list[0] of the last solve, of size m(t0) of that solve (its step 0: the plant's current t)
+  const int m0 = fmpc::stepDims<Problem>(buf, dims, 0, b).m;
+  if constexpr(fmpc::kStepDims<Problem>)
+  {
+    u0.resize(m0, 1);
+  }
+  NMPC_UNROLL
+  for(int a = 0; a < M; a++)
+  {
+    u0[a] = a < m0 ? buf.u[fmpc::at(buf, 0, a, M, b)] : 0.0;
+  }
+  double t = t_plant[b];
+  for(int k = 0; k < substeps; k++)
+  {
+    typename Problem::InputDimVector u = u0;
+    if(use_feedback)
+    {
+      NMPC_UNROLL
+      for(int a = 0; a < M; a++)
+      {
+        if(a < m0)
+        {
+          double acc = 0;
+          NMPC_UNROLL
+          for(int r = 0; r < N; r++)
+          {
+            acc += buf.gain[fmpc::at(buf, 0, GL::K + a + r * M, GL::kStride, b)] * (buf.x[fmpc::at(buf, 0, r, N, b)] - x[r]);
+          }
+          u[a] += acc;
+        }
+      }
+    }
+    x = prob.stateEq(t, x, u, sim_dt);
+    t += sim_dt;
+  }
+  NMPC_UNROLL
+  for(int a = 0; a < N; a++)
+  {
+    x_plant[static_cast<size_t>(a) * buf.B + b] = x[a];
+  }
+  t_plant[b] = t;
+}
+} // namespace fmpc
+
+// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
+// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void fmpc_plant_kernel(FmpcBuffers buf, double * x_plant, double * t_plant, double sim_dt, int substeps, int use_feedback)
 {
@@ -3515,6 +4401,12 @@ __global__ void fmpc_plant_kernel(FmpcBuffers buf, double * x_plant, double * t_
     x_plant[static_cast<size_t>(a) * buf.B + b] = x[a];
   }
   t_plant[b] = t;
+}
+template<class Problem>
+__global__ void fmpc_plant_dims_kernel(FmpcBuffers buf, const int * dims, double * x_plant, double * t_plant, double sim_dt, int substeps,
+                                       int use_feedback)
+{
+  fmpc::plant<Problem>(buf, x_plant, t_plant, sim_dt, substeps, use_feedback, dims);
 }
 } // namespace hip
 } // namespace nmpc_amd

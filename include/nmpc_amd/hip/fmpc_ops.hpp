@@ -66,12 +66,16 @@ inline bool fmpcUseFusedRiccati(int B, int force)
   return (B + 15) / 16 <= fmpcComputeUnits();
 }
 
+/** \param dims (every launch function): the solve's per-step dimensions [2][T][B] ints, written by launch_dims; nullptr (and ignored)
+    for a problem type without time-varying dimensions. */
 struct FmpcOps
 {
   const char * name;
   int state_dim;
-  int input_dim;
-  int ineq_dim;
+  int input_dim; //!< the capacity when the input dimension is time-varying
+  int ineq_dim; //!< the capacity when the inequality dimension is time-varying
+  int dynamic_input; //!< 1: InputDim is nmpc_amd::Dynamic
+  int dynamic_ineq; //!< 1: IneqDim is nmpc_amd::Dynamic
   size_t param_bytes;
   int coef_stride; //!< doubles per timestep of FmpcBuffers::coef
   int gain_stride; //!< doubles per timestep of FmpcBuffers::gain
@@ -80,18 +84,23 @@ struct FmpcOps
   void (*default_params)(void * out);
   //! dt() of a problem object
   double (*dt)(const void * params);
-  hipError_t (*launch_init_complementary)(const FmpcBuffers & buf, hipStream_t stream);
-  hipError_t (*launch_coeff)(const FmpcBuffers & buf, hipStream_t stream);
+  //! inputDim(t), ineqDim(t) of a problem object, evaluated on the host
+  void (*dims_at)(const void * params, double t, int * input_dim, int * ineq_dim);
+  //! fmpc_dims_kernel (problem types with time-varying dimensions; nullptr otherwise)
+  hipError_t (*launch_dims)(const FmpcBuffers & buf, int * dims, hipStream_t stream);
+  hipError_t (*launch_init_complementary)(const FmpcBuffers & buf, const int * dims, hipStream_t stream);
+  hipError_t (*launch_coeff)(const FmpcBuffers & buf, const int * dims, hipStream_t stream);
   hipError_t (*launch_riccati)(const FmpcBuffers & buf, int iter, hipStream_t stream);
-  hipError_t (*launch_delta)(const FmpcBuffers & buf, hipStream_t stream);
+  hipError_t (*launch_delta)(const FmpcBuffers & buf, const int * dims, hipStream_t stream);
   //! fmpc_tail_kernel: step length + update of iteration iter and the head of iteration iter + 1 (barrier parameter, KKT-error terms,
   //! terminal record).  \return hipErrorNotSupported where the sequence does not apply (tail_applies)
   hipError_t (*launch_tail)(const FmpcBuffers & buf, int iter, int last, hipStream_t stream);
   //! whether an iteration of this handle ends in fmpc_tail_kernel: the fused Riccati kernel is the one launched (its producer waves
   //! take over the records' NaN verdict), no line search between step length and update, not switched off (FmpcBuffers::fuse_tail)
   bool (*tail_applies)(const FmpcBuffers & buf);
-  hipError_t (*launch_line_search)(const FmpcBuffers & buf, int iter, hipStream_t stream);
+  hipError_t (*launch_line_search)(const FmpcBuffers & buf, const int * dims, int iter, hipStream_t stream);
   hipError_t (*launch_plant)(const FmpcBuffers & buf,
+                             const int * dims,
                              double * x_plant,
                              double * t_plant,
                              double sim_dt,
@@ -105,7 +114,8 @@ struct FmpcOpsOf
 {
   static constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
   static_assert(std::is_trivially_copyable<Problem>::value, "[FMPC] a problem object must be trivially copyable");
-  static_assert(!Problem::kDynamicInput, "[FMPC] dynamic input dimensions are not offered");
+  //! time-varying dimensions: the dims-aware kernels, the lane Riccati kernel (the quad / fused / tail kernels are for fixed N <= 4, M = 1)
+  static constexpr bool kDims = fmpc::kStepDims<Problem>;
 
   static unsigned blocks(size_t threads, unsigned block)
   {
@@ -120,6 +130,8 @@ struct FmpcOpsOf
     o.state_dim = N;
     o.input_dim = M;
     o.ineq_dim = G;
+    o.dynamic_input = Problem::kDynamicInput ? 1 : 0;
+    o.dynamic_ineq = Problem::kDynamicIneq ? 1 : 0;
     o.param_bytes = sizeof(Problem);
     o.coef_stride = fmpc::CoefLayout<N, M>::kStride;
     o.gain_stride = GL::kStride;
@@ -129,28 +141,59 @@ struct FmpcOpsOf
     o.gain_offset_P = GL::P;
     o.default_params = [](void * out) { new(out) Problem(); };
     o.dt = [](const void * params) { return static_cast<const Problem *>(params)->dt(); };
-    o.launch_init_complementary = [](const FmpcBuffers & buf, hipStream_t stream) {
-      hipLaunchKernelGGL(fmpc_init_complementary_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)), dim3(256),
-                         0, stream, buf);
-      return hipGetLastError();
+    o.dims_at = [](const void * params, double t, int * input_dim, int * ineq_dim) {
+      const Problem & p = *static_cast<const Problem *>(params);
+      *input_dim = p.inputDim(t);
+      *ineq_dim = p.ineqDim(t);
     };
-    o.launch_coeff = [](const FmpcBuffers & buf, hipStream_t stream) {
-      if constexpr(N <= 4 && M == 1)
+    o.launch_dims = nullptr;
+    if constexpr(kDims)
+    {
+      o.launch_dims = [](const FmpcBuffers & buf, int * dims, hipStream_t stream) {
+        hipLaunchKernelGGL(fmpc_dims_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)), dim3(256), 0, stream, buf, dims);
+        return hipGetLastError();
+      };
+    }
+    o.launch_init_complementary = [](const FmpcBuffers & buf, const int * dims, hipStream_t stream) {
+      if constexpr(kDims)
       {
-        if(fmpcUseQuadRiccati(N, M, buf.B, buf.riccati_force) && fmpcUseFusedRiccati(buf.B, buf.riccati_force))
-        {
-          // (the records themselves are computed by the Riccati kernel's producer wave)
-          hipLaunchKernelGGL((fmpc_coeff_kernel<Problem, false>), dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256),
-                             0, stream, buf);
-          return hipGetLastError();
-        }
+        hipLaunchKernelGGL(fmpc_init_complementary_dims_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)), dim3(256),
+                           0, stream, buf, dims);
+        return hipGetLastError();
       }
-      hipLaunchKernelGGL((fmpc_coeff_kernel<Problem, true>), dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
-                         stream, buf);
-      return hipGetLastError();
+      else
+      {
+        hipLaunchKernelGGL(fmpc_init_complementary_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)), dim3(256),
+                           0, stream, buf);
+        return hipGetLastError();
+      }
+    };
+    o.launch_coeff = [](const FmpcBuffers & buf, const int * dims, hipStream_t stream) {
+      if constexpr(kDims)
+      {
+        hipLaunchKernelGGL(fmpc_coeff_dims_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
+                           stream, buf, dims);
+        return hipGetLastError();
+      }
+      else
+      {
+        if constexpr(N <= 4 && M == 1)
+        {
+          if(fmpcUseQuadRiccati(N, M, buf.B, buf.riccati_force) && fmpcUseFusedRiccati(buf.B, buf.riccati_force))
+          {
+            // (the records themselves are computed by the Riccati kernel's producer wave)
+            hipLaunchKernelGGL((fmpc_coeff_kernel<Problem, false>), dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256),
+                               0, stream, buf);
+            return hipGetLastError();
+          }
+        }
+        hipLaunchKernelGGL((fmpc_coeff_kernel<Problem, true>), dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
+                           stream, buf);
+        return hipGetLastError();
+      }
     };
     o.launch_riccati = [](const FmpcBuffers & buf, int iter, hipStream_t stream) {
-      if constexpr(N <= 4 && M == 1)
+      if constexpr(N <= 4 && M == 1 && !kDims)
       {
         if(fmpcUseQuadRiccati(N, M, buf.B, buf.riccati_force))
         {
@@ -168,13 +211,22 @@ struct FmpcOpsOf
       hipLaunchKernelGGL((fmpc_riccati_kernel<N, M>), dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, iter);
       return hipGetLastError();
     };
-    o.launch_delta = [](const FmpcBuffers & buf, hipStream_t stream) {
-      hipLaunchKernelGGL(fmpc_delta_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
-                         stream, buf);
-      return hipGetLastError();
+    o.launch_delta = [](const FmpcBuffers & buf, const int * dims, hipStream_t stream) {
+      if constexpr(kDims)
+      {
+        hipLaunchKernelGGL(fmpc_delta_dims_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
+                           stream, buf, dims);
+        return hipGetLastError();
+      }
+      else
+      {
+        hipLaunchKernelGGL(fmpc_delta_kernel<Problem>, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)), dim3(256), 0,
+                           stream, buf);
+        return hipGetLastError();
+      }
     };
     o.tail_applies = [](const FmpcBuffers & buf) {
-      if constexpr(N <= 4 && M == 1)
+      if constexpr(N <= 4 && M == 1 && !kDims)
       {
         return buf.fuse_tail != 0 && !buf.enable_line_search && fmpc::tailFits(buf) && fmpcUseQuadRiccati(N, M, buf.B, buf.riccati_force)
                && fmpcUseFusedRiccati(buf.B, buf.riccati_force);
@@ -182,7 +234,7 @@ struct FmpcOpsOf
       return false;
     };
     o.launch_tail = [](const FmpcBuffers & buf, int iter, int last, hipStream_t stream) {
-      if constexpr(N <= 4 && M == 1)
+      if constexpr(N <= 4 && M == 1 && !kDims)
       {
         const unsigned dot_bytes = fmpc::tailDotBytes(buf.T);
         hipLaunchKernelGGL(fmpc_tail_kernel<Problem>, dim3(blocks(buf.B, 16)), dim3(16 * fmpc::tailSlices(buf.T)), dot_bytes, stream, buf,
@@ -191,15 +243,32 @@ struct FmpcOpsOf
       }
       return hipErrorNotSupported;
     };
-    o.launch_line_search = [](const FmpcBuffers & buf, int iter, hipStream_t stream) {
-      hipLaunchKernelGGL(fmpc_line_search_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, iter);
-      return hipGetLastError();
+    o.launch_line_search = [](const FmpcBuffers & buf, const int * dims, int iter, hipStream_t stream) {
+      if constexpr(kDims)
+      {
+        hipLaunchKernelGGL(fmpc_line_search_dims_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, dims, iter);
+        return hipGetLastError();
+      }
+      else
+      {
+        hipLaunchKernelGGL(fmpc_line_search_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, iter);
+        return hipGetLastError();
+      }
     };
-    o.launch_plant = [](const FmpcBuffers & buf, double * x_plant, double * t_plant, double sim_dt, int substeps, int use_feedback,
-                        hipStream_t stream) {
-      hipLaunchKernelGGL(fmpc_plant_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, x_plant, t_plant, sim_dt,
-                         substeps, use_feedback);
-      return hipGetLastError();
+    o.launch_plant = [](const FmpcBuffers & buf, const int * dims, double * x_plant, double * t_plant, double sim_dt, int substeps,
+                        int use_feedback, hipStream_t stream) {
+      if constexpr(kDims)
+      {
+        hipLaunchKernelGGL(fmpc_plant_dims_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, dims, x_plant, t_plant,
+                           sim_dt, substeps, use_feedback);
+        return hipGetLastError();
+      }
+      else
+      {
+        hipLaunchKernelGGL(fmpc_plant_kernel<Problem>, dim3(blocks(buf.B, 64)), dim3(64), 0, stream, buf, x_plant, t_plant, sim_dt,
+                           substeps, use_feedback);
+        return hipGetLastError();
+      }
     };
     return o;
   }

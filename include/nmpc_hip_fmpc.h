@@ -25,6 +25,15 @@
  *   GAIN_s     [B][T+1][N]      coeffList()[i].s                                       (FmpcSolver.h:220)
  *   GAIN_P     [B][T+1][N][N]   coeffList()[i].P (symmetric)                           (FmpcSolver.h:223)
  * On the device the same data is kept [step][element][instance]; the conversion happens inside set / get.
+ *
+ * Time-varying dimensions (nmpc_hip_fmpc_model_dynamic): M and G above are the CAPACITIES of the problem type (what
+ * nmpc_hip_fmpc_model_info reports), and step i of instance b has m(i) = inputDim(t_b + i dt) inputs and g(i) = ineqDim(t_b + i dt)
+ * inequality rows, fixed for the whole solve (nmpc_hip_fmpc_get_step_dims).  Every per-step block stays padded to the capacity:
+ *   U [B][T][M], S / NU [B][T][G]: the leading m(i) / g(i) entries of a step are its variable.  A solve neither reads nor writes
+ *       the entries beyond: they keep what set_variable / reset_variable put there, and a row that becomes active in a later
+ *       (warm-started) solve starts from that value.
+ *   GAIN_K: entry (a, c) of step i at c * M + a for a < m(i), and 0 elsewhere.  GAIN_k, DELTA_U, DELTA_S, DELTA_NU and the u0_log
+ *       of nmpc_hip_fmpc_mpc_run follow the same rule: the leading m(i) / g(i) entries, 0 beyond.
  */
 #ifndef NMPC_HIP_FMPC_H
 #define NMPC_HIP_FMPC_H
@@ -217,6 +226,16 @@ extern "C"
 
   /** Names of the gfx950 kernels one iteration launches, comma separated (diagnostics for profiles / bench.py). */
   int nmpc_hip_fmpc_kernel_names(nmpc_hip_fmpc_handle h, const char ** names);
+
+  /** Whether a registered problem type has a time-varying input / inequality dimension (InputDim / IneqDim = nmpc_amd::Dynamic;
+      the reference's Eigen::Dynamic, FmpcSolver.hpp:201-218).  Both 0 for a fixed-dimension problem type. */
+  int nmpc_hip_fmpc_model_dynamic(const char * model, int * dynamic_input, int * dynamic_ineq);
+  /** inputDim(t) and ineqDim(t) of a problem object (params: a blob of param_bytes; NULL = the default object), evaluated on the host.
+      Needs no device. */
+  int nmpc_hip_fmpc_model_dims_at(const char * model, const void * params, size_t bytes, double t, int * input_dim, int * ineq_dim);
+  /** The per-step dimensions the last solve used: input_dims / ineq_dims [B][T] ints (either may be NULL), HOST memory (on_device = 0)
+      or DEVICE memory.  For a fixed-dimension problem type every entry is M / G.  NMPC_HIP_ERR_NOT_SOLVED before the first solve. */
+  int nmpc_hip_fmpc_get_step_dims(nmpc_hip_fmpc_handle h, int * input_dims, int * ineq_dims, int on_device);
 
   /** Text of the last error raised on this thread. */
   const char * nmpc_hip_fmpc_last_error(void);

@@ -17,7 +17,7 @@ LIB_DIR = os.path.join(ROOT, "nmpc_amd", "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libnmpc_hip_ddp.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ("capi.hip", "builtin_models.hip", "model_centroidal.hip", "model_quadrotor.hip", "model_manipulator.hip",
-           "model_quadrotor_f32.hip", "model_cartpole_f32.hip", "model_manipulator_f32.hip", "model_planar_vtol.hip", "fmpc_capi.hip", "fmpc_models.hip",
+           "model_quadrotor_f32.hip", "model_cartpole_f32.hip", "model_manipulator_f32.hip", "model_planar_vtol.hip", "fmpc_capi.hip", "fmpc_models.hip", "fmpc_models_dynamic.hip",
            "cgmres_capi.hip", "cgmres_models.hip")
 ARCH = "gfx950"
 # per-source flags.  builtin_models.hip holds the quad kernel (ddp_kernels_quad.hpp): its fp64 matrix-core results are
@@ -25,6 +25,7 @@ ARCH = "gfx950"
 # use 512 registers gets them in accumulation registers plus ~30 v_accvgpr moves per timestep (-5 % on the headline).
 EXTRA_FLAGS = {"builtin_models.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form"],
                "fmpc_models.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form"],  # fmpc_riccati_quad_kernel: same reason
+               "fmpc_models_dynamic.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form"],  # (same flags as the fixed-dimension FMPC models)
                # C/GMRES: every operation the IEEE operation the source writes (no FMA contraction), as the CPU checker computes it
                "cgmres_capi.hip": ["-ffp-contract=off"], "cgmres_models.hip": ["-ffp-contract=off"]}
 

@@ -103,6 +103,31 @@ __global__ void fmpc_log_kernel(FmpcBuffers buf, int tick, double * x_log, doubl
       it > 0 ? buf.trace[(static_cast<size_t>(b) * buf.max_iter + (it - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_KKT_ERROR] : 0.0;
 }
 
+/** fmpc_log_kernel of a problem with time-varying dimensions: u0_log entries beyond m(0) of the tick's solve are 0. */
+__global__ void fmpc_log_dims_kernel(FmpcBuffers buf, const int * dims, int tick, double * x_log, double * u0_log, int * status_log, int * iter_log,
+                                     double * kkt_log)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if(b >= buf.B)
+  {
+    return;
+  }
+  for(int a = 0; a < buf.N; a++)
+  {
+    x_log[(static_cast<size_t>(tick) * buf.N + a) * buf.B + b] = buf.x0[static_cast<size_t>(a) * buf.B + b];
+  }
+  const int m0 = dims[b];
+  for(int a = 0; a < buf.M; a++)
+  {
+    u0_log[(static_cast<size_t>(tick) * buf.M + a) * buf.B + b] = a < m0 ? buf.u[static_cast<size_t>(a) * buf.B + b] : 0.0;
+  }
+  const int it = buf.iters[b];
+  status_log[static_cast<size_t>(tick) * buf.B + b] = buf.status[b];
+  iter_log[static_cast<size_t>(tick) * buf.B + b] = it;
+  kkt_log[static_cast<size_t>(tick) * buf.B + b] =
+      it > 0 ? buf.trace[(static_cast<size_t>(b) * buf.max_iter + (it - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_KKT_ERROR] : 0.0;
+}
+
 __global__ void fmpc_fill_kernel(double * p, size_t n, double v)
 {
   const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -136,6 +161,7 @@ struct nmpc_hip_fmpc_solver
   std::vector<void *> allocs;
   double * d_t0 = nullptr; // [B]
   double * d_x0 = nullptr; // [N][B]
+  int * d_dims = nullptr; // [2][T][B] per-step input / inequality dimensions of the current solve (time-varying dimensions only)
   void * d_problems = nullptr;
   size_t problems_bytes = 0;
   std::vector<unsigned char> host_problem; // first problem object (dt)
@@ -257,15 +283,29 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
   const unsigned nb = blocks(buf.B, 64);
   h->kev_used = 0;
   h->kev_valid = h->cfg.time_kernels != 0;
+  const int * dims = h->d_dims; // (nullptr: fixed dimensions)
   FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER,
              hipLaunchKernelGGL(nmpc_amd::hip::fmpc_begin_kernel, dim3(nb), dim3(64), 0, stream, buf));
+  if(dims)
+  {
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, FMPC_TRY(ops->launch_dims(buf, h->d_dims, stream)));
+  }
   if(h->cfg.init_complementary_variable)
   {
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, FMPC_TRY(ops->launch_init_complementary(buf, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, FMPC_TRY(ops->launch_init_complementary(buf, dims, stream)));
   }
-  FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER,
-             hipLaunchKernelGGL(nmpc_amd::hip::fmpc_check_variable_kernel, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)),
-                                dim3(256), 0, stream, buf));
+  if(dims)
+  {
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER,
+               hipLaunchKernelGGL(nmpc_amd::hip::fmpc_check_variable_dims_kernel, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)),
+                                  dim3(256), 0, stream, buf, dims));
+  }
+  else
+  {
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER,
+               hipLaunchKernelGGL(nmpc_amd::hip::fmpc_check_variable_kernel, dim3(blocks(static_cast<size_t>(buf.B) * buf.T, 256)),
+                                  dim3(256), 0, stream, buf));
+  }
   // With the fused Riccati kernel and no line search an iteration is three launches: fmpc_tail_kernel closes it (step length, update)
   // and opens the next one (barrier parameter, KKT-error terms, terminal record); the first iteration is opened by the two kernels below.
   const bool tail = ops->tail_applies(buf);
@@ -273,13 +313,22 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
   {
     if(iter == 1 || !tail)
     {
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_BARRIER,
-                 hipLaunchKernelGGL(nmpc_amd::hip::fmpc_barrier_kernel, dim3(nb), dim3(64 * nmpc_amd::hip::fmpc::kSlices), 0, stream, buf,
-                                    iter));
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_COEFF, FMPC_TRY(ops->launch_coeff(buf, stream)));
+      if(dims)
+      {
+        FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_BARRIER,
+                   hipLaunchKernelGGL(nmpc_amd::hip::fmpc_barrier_dims_kernel, dim3(nb), dim3(64 * nmpc_amd::hip::fmpc::kSlices), 0, stream, buf,
+                                      dims, iter));
+      }
+      else
+      {
+        FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_BARRIER,
+                   hipLaunchKernelGGL(nmpc_amd::hip::fmpc_barrier_kernel, dim3(nb), dim3(64 * nmpc_amd::hip::fmpc::kSlices), 0, stream, buf,
+                                      iter));
+      }
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_COEFF, FMPC_TRY(ops->launch_coeff(buf, dims, stream)));
     }
     FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_RICCATI, FMPC_TRY(ops->launch_riccati(buf, iter, stream)));
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_DELTA, FMPC_TRY(ops->launch_delta(buf, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_DELTA, FMPC_TRY(ops->launch_delta(buf, dims, stream)));
     if(tail)
     {
       FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE, FMPC_TRY(ops->launch_tail(buf, iter, iter == h->cfg.max_iter ? 1 : 0, stream)));
@@ -290,11 +339,20 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
                                   buf, iter));
     if(h->cfg.enable_line_search)
     {
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_LINE_SEARCH, FMPC_TRY(ops->launch_line_search(buf, iter, stream)));
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_LINE_SEARCH, FMPC_TRY(ops->launch_line_search(buf, dims, iter, stream)));
     }
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE,
-               hipLaunchKernelGGL(nmpc_amd::hip::fmpc_update_kernel, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)),
-                                  dim3(256), 0, stream, buf));
+    if(dims)
+    {
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE,
+                 hipLaunchKernelGGL(nmpc_amd::hip::fmpc_update_dims_kernel, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)),
+                                    dim3(256), 0, stream, buf, dims));
+    }
+    else
+    {
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE,
+                 hipLaunchKernelGGL(nmpc_amd::hip::fmpc_update_kernel, dim3(blocks(static_cast<size_t>(buf.B) * (buf.T + 1), 256)),
+                                    dim3(256), 0, stream, buf));
+    }
   }
   FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER,
              hipLaunchKernelGGL(nmpc_amd::hip::fmpc_finish_kernel, dim3(nb), dim3(64), 0, stream, buf));
@@ -650,6 +708,10 @@ extern "C"
     if(rc == NMPC_HIP_OK)
     {
       rc = devAllocInt(h, &b.flags, B);
+    }
+    if(rc == NMPC_HIP_OK && m->launch_dims)
+    {
+      rc = devAllocInt(h, &h->d_dims, 2 * T * B);
     }
     if(rc != NMPC_HIP_OK)
     {
@@ -1078,8 +1140,17 @@ extern "C"
       {
         break;
       }
-      hipLaunchKernelGGL(fmpc_log_kernel, dim3(blocks(B, 64)), dim3(64), 0, h->stream, h->buf, k, d_xlog, d_ulog, d_slog, d_ilog, d_klog);
-      if(hipGetLastError() != hipSuccess || h->ops->launch_plant(h->buf, h->d_x0, h->d_t0, sim_dt, sim_substeps, use_feedback, h->stream) != hipSuccess)
+      if(h->d_dims)
+      {
+        hipLaunchKernelGGL(fmpc_log_dims_kernel, dim3(blocks(B, 64)), dim3(64), 0, h->stream, h->buf, h->d_dims, k, d_xlog, d_ulog, d_slog,
+                           d_ilog, d_klog);
+      }
+      else
+      {
+        hipLaunchKernelGGL(fmpc_log_kernel, dim3(blocks(B, 64)), dim3(64), 0, h->stream, h->buf, k, d_xlog, d_ulog, d_slog, d_ilog, d_klog);
+      }
+      if(hipGetLastError() != hipSuccess
+         || h->ops->launch_plant(h->buf, h->d_dims, h->d_x0, h->d_t0, sim_dt, sim_substeps, use_feedback, h->stream) != hipSuccess)
       {
         rc = fail(NMPC_HIP_ERR_HIP, "[FMPC] closed-loop kernel launch failed");
       }
@@ -1166,6 +1237,15 @@ extern "C"
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
     (void)hipSetDevice(h->device);
+    if(h->d_dims)
+    {
+      // time-varying dimensions: the dims-aware kernels around the lane Riccati kernel (fmpc_ops.hpp)
+      h->kernel_names = std::string("fmpc_dims_kernel,fmpc_barrier_dims_kernel,fmpc_coeff_dims_kernel,fmpc_riccati_kernel,fmpc_delta_dims_kernel,"
+                                    "fmpc_step_length_kernel,")
+                        + (h->cfg.enable_line_search ? "fmpc_line_search_dims_kernel," : "") + "fmpc_update_dims_kernel";
+      *names = h->kernel_names.c_str();
+      return NMPC_HIP_OK;
+    }
     h->kernel_names = std::string("fmpc_barrier_kernel,fmpc_coeff_kernel,")
                       + (nmpc_amd::hip::fmpcUseQuadRiccati(h->buf.N, h->buf.M, h->buf.B, h->buf.riccati_force)
                              ? (nmpc_amd::hip::fmpcUseFusedRiccati(h->buf.B, h->buf.riccati_force) ? "fmpc_riccati_fused_kernel" : "fmpc_riccati_quad_kernel")
@@ -1176,6 +1256,98 @@ extern "C"
                              : std::string("fmpc_step_length_kernel,") + (h->cfg.enable_line_search ? "fmpc_line_search_kernel," : "")
                                    + "fmpc_update_kernel");
     *names = h->kernel_names.c_str();
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_fmpc_model_dynamic(const char * model, int * dynamic_input, int * dynamic_ineq)
+  {
+    const FmpcOps * m = findModel(model);
+    if(!m)
+    {
+      return fail(NMPC_HIP_ERR_UNKNOWN_MODEL, std::string("unknown FMPC problem type: ") + (model ? model : "(null)"));
+    }
+    if(dynamic_input)
+    {
+      *dynamic_input = m->dynamic_input;
+    }
+    if(dynamic_ineq)
+    {
+      *dynamic_ineq = m->dynamic_ineq;
+    }
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_fmpc_model_dims_at(const char * model, const void * params, size_t bytes, double t, int * input_dim, int * ineq_dim)
+  {
+    const FmpcOps * m = findModel(model);
+    if(!m)
+    {
+      return fail(NMPC_HIP_ERR_UNKNOWN_MODEL, std::string("unknown FMPC problem type: ") + (model ? model : "(null)"));
+    }
+    if(!input_dim || !ineq_dim || (params && bytes != m->param_bytes))
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FMPC] model_dims_at: NULL output or param blob size mismatch");
+    }
+    std::vector<unsigned char> blob(m->param_bytes);
+    if(params)
+    {
+      std::memcpy(blob.data(), params, m->param_bytes);
+    }
+    else
+    {
+      m->default_params(blob.data());
+    }
+    m->dims_at(blob.data(), t, input_dim, ineq_dim);
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_fmpc_get_step_dims(nmpc_hip_fmpc_handle h, int * input_dims, int * ineq_dims, int on_device)
+  {
+    if(!h)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
+    }
+    if(!h->solved)
+    {
+      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[FMPC] no solve yet");
+    }
+    FMPC_TRY(hipSetDevice(h->device));
+    const int B = h->buf.B, T = h->buf.T;
+    std::vector<int> dev(static_cast<size_t>(2) * T * B);
+    if(h->d_dims)
+    {
+      FMPC_TRY(hipStreamSynchronize(h->stream));
+      FMPC_TRY(hipMemcpy(dev.data(), h->d_dims, dev.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    else
+    {
+      std::fill(dev.begin(), dev.begin() + static_cast<size_t>(T) * B, h->buf.M);
+      std::fill(dev.begin() + static_cast<size_t>(T) * B, dev.end(), h->buf.G);
+    }
+    for(int which = 0; which < 2; which++)
+    {
+      int * out = which == 0 ? input_dims : ineq_dims;
+      if(!out)
+      {
+        continue;
+      }
+      std::vector<int> host(static_cast<size_t>(B) * T); // [T][B] -> [B][T]
+      for(int i = 0; i < T; i++)
+      {
+        for(int b = 0; b < B; b++)
+        {
+          host[static_cast<size_t>(b) * T + i] = dev[(static_cast<size_t>(which) * T + i) * B + b];
+        }
+      }
+      if(on_device)
+      {
+        FMPC_TRY(hipMemcpy(out, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+      }
+      else
+      {
+        std::memcpy(out, host.data(), host.size() * sizeof(int));
+      }
+    }
     return NMPC_HIP_OK;
   }
 

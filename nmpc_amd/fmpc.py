@@ -60,7 +60,7 @@ EXPORTS = (
     "nmpc_hip_fmpc_get_config", "nmpc_hip_fmpc_set_problem", "nmpc_hip_fmpc_set_variable", "nmpc_hip_fmpc_reset_variable",
     "nmpc_hip_fmpc_solve", "nmpc_hip_fmpc_solve_device", "nmpc_hip_fmpc_synchronize", "nmpc_hip_fmpc_get",
     "nmpc_hip_fmpc_field_bytes", "nmpc_hip_fmpc_last_solve_ms", "nmpc_hip_fmpc_last_solve_kernel_ms", "nmpc_hip_fmpc_mpc_run", "nmpc_hip_fmpc_kernel_names",
-    "nmpc_hip_fmpc_last_error",
+    "nmpc_hip_fmpc_model_dynamic", "nmpc_hip_fmpc_model_dims_at", "nmpc_hip_fmpc_get_step_dims", "nmpc_hip_fmpc_last_error",
 )
 
 _declared = False
@@ -94,6 +94,9 @@ def load():
     L.nmpc_hip_fmpc_last_solve_kernel_ms.argtypes = [vp, dp, ip]
     L.nmpc_hip_fmpc_mpc_run.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_int, C.c_int, dp, dp, ip, ip, dp, dp, dp]
     L.nmpc_hip_fmpc_kernel_names.argtypes = [vp, C.POINTER(C.c_char_p)]
+    L.nmpc_hip_fmpc_model_dynamic.argtypes = [C.c_char_p, ip, ip]
+    L.nmpc_hip_fmpc_model_dims_at.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_double, ip, ip]
+    L.nmpc_hip_fmpc_get_step_dims.argtypes = [vp, ip, ip, C.c_int]
     L.nmpc_hip_fmpc_last_error.argtypes = []
     L.nmpc_hip_fmpc_last_error.restype = C.c_char_p
     for name in EXPORTS:
@@ -124,10 +127,26 @@ def model_names():
 
 
 def model_info(model: str):
-    """(state_dim, input_dim, ineq_dim, param_bytes)."""
+    """(state_dim, input_dim, ineq_dim, param_bytes); input_dim / ineq_dim are the capacities of a time-varying dimension."""
     n, m, g, pb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
     check(load().nmpc_hip_fmpc_model_info(model.encode(), C.byref(n), C.byref(m), C.byref(g), C.byref(pb)))
     return n.value, m.value, g.value, pb.value
+
+
+def model_dynamic(model: str):
+    """(dynamic_input, dynamic_ineq): whether the input / inequality dimension of the problem type varies with t."""
+    di, dg = C.c_int(), C.c_int()
+    check(load().nmpc_hip_fmpc_model_dynamic(model.encode(), C.byref(di), C.byref(dg)))
+    return di.value, dg.value
+
+
+def model_dims_at(model: str, t: float, params: Optional[bytes] = None):
+    """(inputDim(t), ineqDim(t)) of a problem object (None: the default object), evaluated on the host."""
+    m, g = C.c_int(), C.c_int()
+    buf = None if params is None else (C.c_ubyte * len(params)).from_buffer_copy(params)
+    check(load().nmpc_hip_fmpc_model_dims_at(model.encode(), buf, 0 if params is None else len(params), float(t), C.byref(m),
+                                             C.byref(g)))
+    return m.value, g.value
 
 
 class FmpcProblem:
@@ -156,6 +175,15 @@ class FmpcProblem:
 
     def ineqDim(self) -> int:
         return self.ineq_dim
+
+    @property
+    def dynamic(self) -> bool:
+        """Whether the input or inequality dimension varies with t (inputDim() / ineqDim() are then the capacities)."""
+        return any(model_dynamic(self.model))
+
+    def dimsAt(self, t: float):
+        """(inputDim(t), ineqDim(t)) of this problem object."""
+        return model_dims_at(self.model, t, self.blob())
 
     def blob(self) -> bytes:
         return np.ascontiguousarray(self.p, dtype=np.float64).tobytes()
@@ -187,6 +215,21 @@ class FmpcProblemPointMass(FmpcProblem):
 
     def __init__(self, dt: float = 0.02):
         super().__init__("fmpc_pointmass", dt)
+
+
+class FmpcProblemVerticalMotion(FmpcProblem):
+    """nmpc_amd::FmpcProblemVerticalMotion (include/nmpc_amd/models/FmpcVerticalMotion.hpp): time-varying input and inequality
+    dimensions, one contact force per contact (1, 2 in (2, 3), 0 in (4.5, 5), then 1 again), 0 <= f_j <= f_max.  Image: dt,
+    running_x[2], running_u, terminal_x[2], mass, f_min, f_max, ref_switch_t, double_support_begin, double_support_end,
+    flight_begin, flight_end."""
+
+    FIELDS = ("dt", "running_x0", "running_x1", "running_u", "terminal_x0", "terminal_x1", "mass", "f_min", "f_max", "ref_switch_t",
+              "double_support_begin", "double_support_end", "flight_begin", "flight_end")
+
+    def __init__(self, dt: float = 0.01, **kw):
+        super().__init__("fmpc_vertical", dt)
+        for k, v in kw.items():
+            self.p[self.FIELDS.index(k)] = v
 
 
 class Configuration:
@@ -432,6 +475,23 @@ class FmpcSolverBatch:
                                             out["iters"].ctypes.data_as(ip), out["kkt_error"].ctypes.data_as(dp),
                                             out["x_final"].ctypes.data_as(dp), out["t_final"].ctypes.data_as(dp)))
         return out
+
+    def _stepDims(self, which: int) -> np.ndarray:
+        T, B = self._config.horizon_steps, self.batch
+        out = np.zeros((B, T), dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        ptrs = [None, None]
+        ptrs[which] = out.ctypes.data_as(ip)
+        check(self._L.nmpc_hip_fmpc_get_step_dims(self._h, ptrs[0], ptrs[1], 0))
+        return out
+
+    def inputDimList(self) -> np.ndarray:
+        """[B][T]: the input dimension of every step in the last solve (inputDim(t + i dt))."""
+        return self._stepDims(0)
+
+    def ineqDimList(self) -> np.ndarray:
+        """[B][T]: the inequality dimension of every step in the last solve (ineqDim(t + i dt))."""
+        return self._stepDims(1)
 
     def kernelNames(self):
         p = C.c_char_p()
