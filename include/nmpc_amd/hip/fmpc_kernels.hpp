@@ -436,7 +436,16 @@ __device__ __forceinline__ void loadVec(const double * base, const FmpcBuffers &
     kernels below, FmpcOpsOf): they read the dimensions of every step from the solve's dims array [2][T][B] ints (input, then
     inequality dimension), which fmpc_dims_kernel writes once when the solve begins, and touch the leading m(i) inputs and g(i)
     rows of the capacity-sized arrays only.  The array is a kernel argument of its own, not a member of FmpcBuffers: appending a
-    member moves the hidden kernel arguments and every argument after the struct, which changes the code of every existing kernel. */
+    member moves the hidden kernel arguments and every argument after the struct, which changes the code of every existing kernel.
+
+    Every statement of the iteration exists once: a fixed-dimension kernel and its `_dims` twin are entry points over one body
+    (fmpc::initComplementary / coeff / delta / lineSearch / plant here, checkVariable / barrier / update / logRow for the problem-
+    independent kernels), the fixed-dimension one passing dims = nullptr.  For a fixed-dimension problem stepDims() returns the
+    capacities as compile-time constants, so every guard `a < d.m` / `j < d.g` folds away and dims is never read.  [compiled for
+    gfx950 next to separately written fixed-dimension bodies: the coefficient, barrier and update kernels come out instruction for
+    instruction the same, init and plant as the same instructions in another order, delta and line search with the same floating-
+    point instructions and 5 - 10 % fewer instructions of control flow; no scratch, no occupancy step crossed.
+    scripts/fmpc_lib_ab.py compares two builds of the library on a GPU: every returned array bit for bit, and the kernel times.] */
 template<class Problem>
 constexpr bool kStepDims = Problem::kDynamicInput || Problem::kDynamicIneq;
 
@@ -497,9 +506,17 @@ __global__ void fmpc_begin_kernel(FmpcBuffers buf)
   }
 }
 
-/** checkVariable's non-negativity test (FmpcSolver.hpp:338-353): the reference throws std::runtime_error; here the instance
-    gets NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE and is skipped, the C-ABI call reports NMPC_HIP_ERR_RUNTIME afterwards. */
-__global__ void fmpc_check_variable_kernel(FmpcBuffers buf)
+namespace fmpc
+{
+// The three problem-independent kernels that loop over the inputs or inequality rows exist in two variants: fixed dimensions
+// (kDims = false: the handle's M and G, dims is not read) and time-varying dimensions (kDims = true: the leading m(i) / g(i) of
+// every step, dims: [2][T][B], fmpc_dims_kernel; entries beyond a step's dimensions are neither read nor written).
+
+/** checkVariable's non-negativity test (FmpcSolver.hpp:338-353, over s_list[i], nu_list[i] of size ineqDim(t)): the reference throws
+    std::runtime_error; here the instance gets NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE and is skipped, the C-ABI call reports
+    NMPC_HIP_ERR_RUNTIME afterwards. */
+template<bool kDims>
+__device__ __forceinline__ void checkVariable(const FmpcBuffers & buf, const int * dims)
 {
   const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if(tid >= static_cast<size_t>(buf.B) * buf.T)
@@ -508,41 +525,61 @@ __global__ void fmpc_check_variable_kernel(FmpcBuffers buf)
   }
   const int b = static_cast<int>(tid % buf.B);
   const int i = static_cast<int>(tid / buf.B);
+  int g = buf.G;
+  if constexpr(kDims)
+  {
+    g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+  }
   bool negative = false;
   double dot = 0; // s_list[i] . nu_list[i]: what the first iteration's barrier update sums (later ones: fmpc_update_kernel)
-  for(int j = 0; j < buf.G; j++)
+  for(int j = 0; j < g; j++)
   {
-    const double sv = buf.s[fmpc::at(buf, i, j, buf.G, b)], nv = buf.nu[fmpc::at(buf, i, j, buf.G, b)];
+    const double sv = buf.s[at(buf, i, j, buf.G, b)], nv = buf.nu[at(buf, i, j, buf.G, b)];
     negative = negative || sv < 0 || nv < 0;
     dot += sv * nv;
   }
-  buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
+  buf.part[at(buf, i, 3, kPartSlots, b)] = dot;
   if(negative)
   {
     buf.status[b] = NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE; // every writer stores the same value
   }
 }
 
-/** Barrier parameter of the iteration, (19.19) in Nocedal & Wright (FmpcSolver.hpp:370-392); also opens the iteration's trace
-    row (:363-366).  Block = 64 instances x kSlices horizon slices. */
-__global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_kernel(FmpcBuffers buf, int iter)
+/** Barrier parameter of the iteration, (19.19) in Nocedal & Wright (FmpcSolver.hpp:370-392 sums the per-step dot products and
+    counts the rows of every s_list[i]); also opens the iteration's trace row (:363-366).  Block = 64 instances x kSlices horizon
+    slices.  The mean of s . nu is the sum divided by T G, with time-varying dimensions by sum_i g(i), counted beside the sum (no
+    active row in the whole horizon: 0 / 0, as the reference). */
+template<bool kDims>
+__device__ __forceinline__ void barrier(const FmpcBuffers & buf, const int * dims, int iter)
 {
-  __shared__ double sh[fmpc::kSlices][64];
+  __shared__ double sh[kSlices][64];
   const int lane = threadIdx.x & 63;
   const int q = threadIdx.x >> 6;
   const int b = blockIdx.x * 64 + lane;
-  const bool act = b < buf.B && buf.status[b] == fmpc::kStatusContinued;
+  const bool act = b < buf.B && buf.status[b] == kStatusContinued;
   double acc = 0;
+  int rows = 0;
   if(act && buf.update_barrier_eps)
   {
-    const int chunk = (buf.T + fmpc::kSlices - 1) / fmpc::kSlices;
+    const int chunk = (buf.T + kSlices - 1) / kSlices;
     const int i1 = min(buf.T, (q + 1) * chunk);
     for(int i = q * chunk; i < i1; i++)
     {
-      acc += buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)]; // s_list[i] . nu_list[i], left by the kernel that wrote s, nu
+      acc += buf.part[at(buf, i, 3, kPartSlots, b)]; // s_list[i] . nu_list[i], left by the kernel that wrote s, nu
+      if constexpr(kDims)
+      {
+        rows += dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+      }
     }
   }
   sh[q][lane] = acc;
+  int(*shn)[64] = nullptr; // the slices' row counts: allocated with time-varying dimensions only
+  if constexpr(kDims)
+  {
+    __shared__ int sh_rows[kSlices][64];
+    shn = sh_rows;
+    shn[q][lane] = rows;
+  }
   syncThreadsFuzzed(__LINE__);
   if(q == 0 && act)
   {
@@ -550,11 +587,23 @@ __global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_kernel(FmpcBu
     if(buf.update_barrier_eps)
     {
       double s_nu_ave = 0;
-      for(int k = 0; k < fmpc::kSlices; k++)
+      int n_rows = 0;
+      for(int k = 0; k < kSlices; k++)
       {
         s_nu_ave += sh[k][lane];
+        if constexpr(kDims)
+        {
+          n_rows += shn[k][lane];
+        }
       }
-      s_nu_ave /= static_cast<double>(buf.T * buf.G);
+      if constexpr(kDims)
+      {
+        s_nu_ave /= static_cast<double>(n_rows);
+      }
+      else
+      {
+        s_nu_ave /= static_cast<double>(buf.T * buf.G);
+      }
       constexpr double sigma = 0.5;
       constexpr double barrier_eps_min = 1e-8;
       constexpr double barrier_eps_max = 1e6;
@@ -569,6 +618,24 @@ __global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_kernel(FmpcBu
     row[NMPC_HIP_FMPC_TRACE_ITER] = iter;
     row[NMPC_HIP_FMPC_TRACE_BARRIER_EPS] = eps;
   }
+}
+} // namespace fmpc
+
+__global__ void fmpc_check_variable_kernel(FmpcBuffers buf)
+{
+  fmpc::checkVariable<false>(buf, nullptr);
+}
+__global__ void fmpc_check_variable_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  fmpc::checkVariable<true>(buf, dims);
+}
+__global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_kernel(FmpcBuffers buf, int iter)
+{
+  fmpc::barrier<false>(buf, nullptr, iter);
+}
+__global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_dims_kernel(FmpcBuffers buf, const int * dims, int iter)
+{
+  fmpc::barrier<true>(buf, dims, iter);
 }
 
 /** Fraction-to-boundary rule (FmpcSolver.hpp:713-742): minimum of the per-timestep candidates, validity test; and the verdict
@@ -623,8 +690,11 @@ __global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_step_length_kernel(Fm
   }
 }
 
+namespace fmpc
+{
 /** Variable update (FmpcSolver.hpp:801-835), one thread per (instance, timestep). */
-__global__ void fmpc_update_kernel(FmpcBuffers buf)
+template<bool kDims>
+__device__ __forceinline__ void update(const FmpcBuffers & buf, const int * dims)
 {
   const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
@@ -633,7 +703,7 @@ __global__ void fmpc_update_kernel(FmpcBuffers buf)
   }
   const int b = static_cast<int>(tid % buf.B);
   const int i = static_cast<int>(tid / buf.B);
-  if(buf.status[b] != fmpc::kStatusContinued)
+  if(buf.status[b] != kStatusContinued)
   {
     return;
   }
@@ -641,15 +711,21 @@ __global__ void fmpc_update_kernel(FmpcBuffers buf)
   const double alpha_nu = buf.alpha[1 * buf.B + b];
   for(int e = 0; e < buf.N; e++)
   {
-    const size_t k = fmpc::at(buf, i, e, buf.N, b);
+    const size_t k = at(buf, i, e, buf.N, b);
     buf.x[k] += alpha_s * buf.dx[k];
     buf.lam[k] += alpha_nu * buf.dlam[k];
   }
   if(i < buf.T)
   {
-    for(int e = 0; e < buf.M; e++)
+    int m = buf.M, g = buf.G;
+    if constexpr(kDims)
     {
-      const size_t k = fmpc::at(buf, i, e, buf.M, b);
+      m = dims[static_cast<size_t>(i) * buf.B + b];
+      g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
+    }
+    for(int e = 0; e < m; e++)
+    {
+      const size_t k = at(buf, i, e, buf.M, b);
       buf.u[k] += alpha_s * buf.du[k];
     }
     // the reference clamps at numeric_limits<double>::lowest() (= -DBL_MAX, FmpcSolver.hpp:812) when an entry went negative:
@@ -657,173 +733,9 @@ __global__ void fmpc_update_kernel(FmpcBuffers buf)
     constexpr double min_positive_value = -DBL_MAX;
     bool s_neg = false, nu_neg = false;
     double dot = 0; // s . nu of the updated timestep, for the next iteration's barrier update (FmpcSolver.hpp:376-380)
-    for(int e = 0; e < buf.G; e++)
-    {
-      const size_t k = fmpc::at(buf, i, e, buf.G, b);
-      const double sv = buf.s[k] + alpha_s * buf.ds[k];
-      const double nv = buf.nu[k] + alpha_nu * buf.dnu[k];
-      buf.s[k] = sv;
-      buf.nu[k] = nv;
-      dot += sv * nv;
-      s_neg = s_neg || sv < 0;
-      nu_neg = nu_neg || nv < 0;
-    }
-    if(s_neg || nu_neg)
-    {
-      dot = 0;
-      for(int e = 0; e < buf.G; e++)
-      {
-        const size_t k = fmpc::at(buf, i, e, buf.G, b);
-        double sv = buf.s[k], nv = buf.nu[k];
-        if(s_neg && sv < min_positive_value)
-        {
-          sv = min_positive_value;
-          buf.s[k] = sv;
-        }
-        if(nu_neg && nv < min_positive_value)
-        {
-          nv = min_positive_value;
-          buf.nu[k] = nv;
-        }
-        dot += sv * nv;
-      }
-    }
-    buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
-  }
-}
-
-/** End of solve (FmpcSolver.hpp:233-246): IterationContinued becomes MaxIterationReached; with max_iter = 0 the loop never
-    ran and solve() returns the initial Status::Uninitialized. */
-__global__ void fmpc_finish_kernel(FmpcBuffers buf)
-{
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if(b < buf.B && buf.status[b] == fmpc::kStatusContinued)
-  {
-    buf.status[b] = buf.max_iter > 0 ? 5 : 0; // Status::MaxIterationReached : Status::Uninitialized
-  }
-}
-
-// ---- the problem-independent kernels of a problem with time-varying dimensions: the three above that loop over the inputs or
-// inequality rows, restricted to the leading m(i) / g(i) of every step (dims: [2][T][B], fmpc_dims_kernel).  Entries beyond a step's
-// dimensions are neither read nor written.
-
-/** fmpc_check_variable_kernel over the active rows: a negative s or nu beyond g(i) is not looked at (FmpcSolver.hpp:338-353 checks
-    s_list[i], nu_list[i] of size ineqDim(t)). */
-__global__ void fmpc_check_variable_dims_kernel(FmpcBuffers buf, const int * dims)
-{
-  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if(tid >= static_cast<size_t>(buf.B) * buf.T)
-  {
-    return;
-  }
-  const int b = static_cast<int>(tid % buf.B);
-  const int i = static_cast<int>(tid / buf.B);
-  const int g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
-  bool negative = false;
-  double dot = 0;
-  for(int j = 0; j < g; j++)
-  {
-    const double sv = buf.s[fmpc::at(buf, i, j, buf.G, b)], nv = buf.nu[fmpc::at(buf, i, j, buf.G, b)];
-    negative = negative || sv < 0 || nv < 0;
-    dot += sv * nv;
-  }
-  buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
-  if(negative)
-  {
-    buf.status[b] = NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE;
-  }
-}
-
-/** fmpc_barrier_kernel with the mean of s . nu over the active rows: the sum divided by sum_i g(i) (FmpcSolver.hpp:370-392 sums the
-    per-step dot products and counts the rows of every s_list[i]).  No active row in the whole horizon: 0 / 0, as the reference. */
-__global__ void __launch_bounds__(64 * fmpc::kSlices) fmpc_barrier_dims_kernel(FmpcBuffers buf, const int * dims, int iter)
-{
-  __shared__ double sh[fmpc::kSlices][64];
-  __shared__ int shn[fmpc::kSlices][64];
-  const int lane = threadIdx.x & 63;
-  const int q = threadIdx.x >> 6;
-  const int b = blockIdx.x * 64 + lane;
-  const bool act = b < buf.B && buf.status[b] == fmpc::kStatusContinued;
-  double acc = 0;
-  int rows = 0;
-  if(act && buf.update_barrier_eps)
-  {
-    const int chunk = (buf.T + fmpc::kSlices - 1) / fmpc::kSlices;
-    const int i1 = min(buf.T, (q + 1) * chunk);
-    for(int i = q * chunk; i < i1; i++)
-    {
-      acc += buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)];
-      rows += dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
-    }
-  }
-  sh[q][lane] = acc;
-  shn[q][lane] = rows;
-  syncThreadsFuzzed(__LINE__);
-  if(q == 0 && act)
-  {
-    double eps = buf.barrier_eps[b];
-    if(buf.update_barrier_eps)
-    {
-      double s_nu_ave = 0;
-      int n_rows = 0;
-      for(int k = 0; k < fmpc::kSlices; k++)
-      {
-        s_nu_ave += sh[k][lane];
-        n_rows += shn[k][lane];
-      }
-      s_nu_ave /= static_cast<double>(n_rows);
-      constexpr double sigma = 0.5;
-      constexpr double barrier_eps_min = 1e-8;
-      constexpr double barrier_eps_max = 1e6;
-      const double v = sigma * s_nu_ave;
-      eps = (v < barrier_eps_min) ? barrier_eps_min : ((barrier_eps_max < v) ? barrier_eps_max : v);
-      buf.barrier_eps[b] = eps;
-    }
-    buf.iters[b] = iter;
-    buf.flags[b] = 0;
-    double * row = buf.trace + (static_cast<size_t>(b) * buf.max_iter + (iter - 1)) * NMPC_HIP_FMPC_NTRACE;
-    row[NMPC_HIP_FMPC_TRACE_ITER] = iter;
-    row[NMPC_HIP_FMPC_TRACE_BARRIER_EPS] = eps;
-  }
-}
-
-/** fmpc_update_kernel over the leading m(i) inputs and g(i) rows of every step. */
-__global__ void fmpc_update_dims_kernel(FmpcBuffers buf, const int * dims)
-{
-  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
-  {
-    return;
-  }
-  const int b = static_cast<int>(tid % buf.B);
-  const int i = static_cast<int>(tid / buf.B);
-  if(buf.status[b] != fmpc::kStatusContinued)
-  {
-    return;
-  }
-  const double alpha_s = buf.alpha[2 * buf.B + b];
-  const double alpha_nu = buf.alpha[1 * buf.B + b];
-  for(int e = 0; e < buf.N; e++)
-  {
-    const size_t k = fmpc::at(buf, i, e, buf.N, b);
-    buf.x[k] += alpha_s * buf.dx[k];
-    buf.lam[k] += alpha_nu * buf.dlam[k];
-  }
-  if(i < buf.T)
-  {
-    const int m = dims[static_cast<size_t>(i) * buf.B + b];
-    const int g = dims[(static_cast<size_t>(buf.T) + i) * buf.B + b];
-    for(int e = 0; e < m; e++)
-    {
-      const size_t k = fmpc::at(buf, i, e, buf.M, b);
-      buf.u[k] += alpha_s * buf.du[k];
-    }
-    constexpr double min_positive_value = -DBL_MAX;
-    bool s_neg = false, nu_neg = false;
-    double dot = 0;
     for(int e = 0; e < g; e++)
     {
-      const size_t k = fmpc::at(buf, i, e, buf.G, b);
+      const size_t k = at(buf, i, e, buf.G, b);
       const double sv = buf.s[k] + alpha_s * buf.ds[k];
       const double nv = buf.nu[k] + alpha_nu * buf.dnu[k];
       buf.s[k] = sv;
@@ -837,7 +749,7 @@ __global__ void fmpc_update_dims_kernel(FmpcBuffers buf, const int * dims)
       dot = 0;
       for(int e = 0; e < g; e++)
       {
-        const size_t k = fmpc::at(buf, i, e, buf.G, b);
+        const size_t k = at(buf, i, e, buf.G, b);
         double sv = buf.s[k], nv = buf.nu[k];
         if(s_neg && sv < min_positive_value)
         {
@@ -852,7 +764,28 @@ __global__ void fmpc_update_dims_kernel(FmpcBuffers buf, const int * dims)
         dot += sv * nv;
       }
     }
-    buf.part[fmpc::at(buf, i, 3, fmpc::kPartSlots, b)] = dot;
+    buf.part[at(buf, i, 3, kPartSlots, b)] = dot;
+  }
+}
+} // namespace fmpc
+
+__global__ void fmpc_update_kernel(FmpcBuffers buf)
+{
+  fmpc::update<false>(buf, nullptr);
+}
+__global__ void fmpc_update_dims_kernel(FmpcBuffers buf, const int * dims)
+{
+  fmpc::update<true>(buf, dims);
+}
+
+/** End of solve (FmpcSolver.hpp:233-246): IterationContinued becomes MaxIterationReached; with max_iter = 0 the loop never
+    ran and solve() returns the initial Status::Uninitialized. */
+__global__ void fmpc_finish_kernel(FmpcBuffers buf)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if(b < buf.B && buf.status[b] == fmpc::kStatusContinued)
+  {
+    buf.status[b] = buf.max_iter > 0 ? 5 : 0; // Status::MaxIterationReached : Status::Uninitialized
   }
 }
 
@@ -972,46 +905,10 @@ __device__ __forceinline__ void initComplementary(const FmpcBuffers & buf, const
 }
 } // namespace fmpc
 
-/** init_complementary_variable (FmpcSolver.hpp:170-187). */
-// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
-// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void fmpc_init_complementary_kernel(FmpcBuffers buf)
 {
-  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
-  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if(tid >= static_cast<size_t>(buf.B) * buf.T)
-  {
-    return;
-  }
-  const int b = static_cast<int>(tid % buf.B);
-  const int i = static_cast<int>(tid / buf.B);
-  constexpr double initial_barrier_eps = 1e-4;
-  constexpr double complementary_variable_margin_rate = 1e-2;
-  constexpr double complementary_variable_min = 1e-2;
-  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
-  typename Problem::StateDimVector x;
-  typename Problem::InputDimVector u;
-  fmpc::loadVec(buf.x, buf, i, b, x);
-  fmpc::loadVec(buf.u, buf, i, b, u);
-  const double t = buf.t0[b] + i * prob.dt();
-  const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
-  NMPC_UNROLL
-  for(int j = 0; j < G; j++)
-  {
-    const double neg_g = -1 * g[j];
-    const double sj = (1.0 + complementary_variable_margin_rate) * (neg_g < complementary_variable_min ? complementary_variable_min : neg_g);
-    const double r = initial_barrier_eps * (1.0 / sj);
-    buf.s[fmpc::at(buf, i, j, G, b)] = sj;
-    buf.nu[fmpc::at(buf, i, j, G, b)] =
-        (1.0 + complementary_variable_margin_rate) * (r < complementary_variable_min ? complementary_variable_min : r);
-  }
-  if(i == 0)
-  {
-    buf.barrier_eps[b] = initial_barrier_eps;
-  }
-  (void)N;
-  (void)M;
+  fmpc::initComplementary<Problem>(buf, nullptr);
 }
 template<class Problem>
 __global__ void fmpc_init_complementary_dims_kernel(FmpcBuffers buf, const int * dims)
@@ -1435,13 +1332,9 @@ struct GlobalCoefSink
   }
   __device__ __forceinline__ void midpoint() const {}
 };
-} // namespace fmpc
-
-/** One thread per (instance, timestep): the coefficient record, the KKT-error terms, the NaN flag.
-    \tparam kRecord false: everything but the record — what is launched in front of fmpc_riccati_fused_kernel, whose producer wave
-    computes the records into its staging LDS (A, B, x_bar also to HBM, for the forward sweep) */
-template<class Problem, bool kRecord = true>
-__global__ void __launch_bounds__(256) fmpc_coeff_kernel(FmpcBuffers buf)
+/** One thread per (instance, timestep): the coefficient record, the KKT-error terms, the NaN flag — everything to HBM. */
+template<class Problem, bool kRecord>
+__device__ __forceinline__ void coeff(const FmpcBuffers & buf, const int * dims)
 {
   constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax;
   const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -1451,36 +1344,30 @@ __global__ void __launch_bounds__(256) fmpc_coeff_kernel(FmpcBuffers buf)
   }
   const int b = static_cast<int>(tid % buf.B);
   const int i = static_cast<int>(tid / buf.B);
-  if(buf.status[b] != fmpc::kStatusContinued)
+  if(buf.status[b] != kStatusContinued)
   {
     return;
   }
-  fmpc::GlobalCoefSink<N, M, kRecord> sink{buf, b, i};
-  fmpc::CoefInputs<Problem> in;
-  fmpc::loadCoefInputs<Problem>(buf, b, i, in);
-  fmpc::coefficients<Problem>(buf, b, i, in, sink);
+  GlobalCoefSink<N, M, kRecord> sink{buf, b, i};
+  CoefInputs<Problem> in;
+  loadCoefInputs<Problem>(buf, b, i, in, dims);
+  coefficients<Problem>(buf, b, i, in, sink, dims);
+}
+} // namespace fmpc
+
+/** \tparam kRecord false: everything but the record — what is launched in front of fmpc_riccati_fused_kernel, whose producer wave
+    computes the records into its staging LDS (A, B, x_bar also to HBM, for the forward sweep) */
+template<class Problem, bool kRecord = true>
+__global__ void __launch_bounds__(256) fmpc_coeff_kernel(FmpcBuffers buf)
+{
+  fmpc::coeff<Problem, kRecord>(buf, nullptr);
 }
 
 /** fmpc_coeff_kernel of a problem with time-varying dimensions (dims: fmpc_dims_kernel). */
 template<class Problem>
 __global__ void __launch_bounds__(256) fmpc_coeff_dims_kernel(FmpcBuffers buf, const int * dims)
 {
-  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax;
-  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
-  {
-    return;
-  }
-  const int b = static_cast<int>(tid % buf.B);
-  const int i = static_cast<int>(tid / buf.B);
-  if(buf.status[b] != fmpc::kStatusContinued)
-  {
-    return;
-  }
-  fmpc::GlobalCoefSink<N, M, true> sink{buf, b, i};
-  fmpc::CoefInputs<Problem> in;
-  fmpc::loadCoefInputs<Problem>(buf, b, i, in, dims);
-  fmpc::coefficients<Problem>(buf, b, i, in, sink, dims);
+  fmpc::coeff<Problem, true>(buf, dims);
 }
 
 namespace fmpc
@@ -3614,106 +3501,10 @@ __device__ __forceinline__ void delta(const FmpcBuffers & buf, const int * dims)
 }
 } // namespace fmpc
 
-// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
-// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void __launch_bounds__(256) fmpc_delta_kernel(FmpcBuffers buf)
 {
-  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
-  const size_t tid = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  using GL = fmpc::GainLayout<N, M>;
-  if(tid >= static_cast<size_t>(buf.B) * (buf.T + 1))
-  {
-    return;
-  }
-  const int b = static_cast<int>(tid % buf.B);
-  const int i = static_cast<int>(tid / buf.B);
-  if(buf.status[b] != fmpc::kStatusContinued)
-  {
-    return;
-  }
-  typename Problem::StateDimVector x, dx;
-  fmpc::loadVec(buf.dx, buf, i, b, dx);
-  bool nan = false;
-  NMPC_UNROLL
-  for(int a = 0; a < N; a++) // (2.33)
-  {
-    double acc = 0;
-    NMPC_UNROLL
-    for(int r = 0; r < N; r++)
-    {
-      acc += buf.gain[fmpc::at(buf, i, GL::P + a + r * N, GL::kStride, b)] * dx[r];
-    }
-    const double dl = acc - buf.gain[fmpc::at(buf, i, GL::S + a, GL::kStride, b)];
-    buf.dlam[fmpc::at(buf, i, a, N, b)] = dl;
-    nan = nan || fmpc::bad(dl) || fmpc::bad(dx[a]);
-  }
-  if(i == buf.T)
-  {
-    if(nan)
-    {
-      atomicOr(&buf.flags[b], 2);
-    }
-    return;
-  }
-  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
-  const double t = buf.t0[b] + i * prob.dt();
-  typename Problem::InputDimVector u, du;
-  typename Problem::IneqDimVector s, nu;
-  fmpc::loadVec(buf.x, buf, i, b, x);
-  fmpc::loadVec(buf.u, buf, i, b, u);
-  fmpc::loadVec(buf.du, buf, i, b, du);
-  NMPC_UNROLL
-  for(int a = 0; a < M; a++)
-  {
-    nan = nan || fmpc::bad(du[a]);
-  }
-  fmpc::loadVec(buf.s, buf, i, b, s);
-  fmpc::loadVec(buf.nu, buf, i, b, nu);
-  typename Problem::IneqStateDimMatrix C;
-  typename Problem::IneqInputDimMatrix D;
-  prob.calcIneqConstDeriv(t, x, u, C, D);
-  const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
-  const double barrier_eps = buf.barrier_eps[b];
-  constexpr double margin_ratio = 0.995;
-  double alpha_s = 1.0, alpha_nu = 1.0;
-  NMPC_UNROLL
-  for(int j = 0; j < G; j++)
-  {
-    double cx = 0, dd = 0;
-    NMPC_UNROLL
-    for(int r = 0; r < N; r++)
-    {
-      cx += C(j, r) * dx[r];
-    }
-    NMPC_UNROLL
-    for(int r = 0; r < M; r++)
-    {
-      dd += D(j, r) * du[r];
-    }
-    const double g_bar = g[j] + s[j];
-    const double dsj = -1 * ((cx + dd) + g_bar); // (2.27a)
-    const double dnj = -1 * (nu[j] * (dsj + s[j]) - barrier_eps) / s[j]; // (2.27b)
-    buf.ds[fmpc::at(buf, i, j, G, b)] = dsj;
-    buf.dnu[fmpc::at(buf, i, j, G, b)] = dnj;
-    nan = nan || fmpc::bad(dsj) || fmpc::bad(dnj);
-    if(dsj < 0) // (19.9) in Nocedal & Wright
-    {
-      const double c = -1 * margin_ratio * s[j] / dsj;
-      alpha_s = (c < alpha_s) ? c : alpha_s;
-    }
-    if(dnj < 0)
-    {
-      const double c = -1 * margin_ratio * nu[j] / dnj;
-      alpha_nu = (c < alpha_nu) ? c : alpha_nu;
-    }
-  }
-  buf.part[fmpc::at(buf, i, 1, fmpc::kPartSlots, b)] = alpha_s;
-  buf.part[fmpc::at(buf, i, 2, fmpc::kPartSlots, b)] = alpha_nu;
-  if(nan)
-  {
-    atomicOr(&buf.flags[b], 2);
-  }
+  fmpc::delta<Problem>(buf, nullptr);
 }
 /** fmpc_delta_kernel of a problem with time-varying dimensions: rows beyond g(i) get ds = dnu = 0 and no step-length candidate. */
 template<class Problem>
@@ -4027,252 +3818,10 @@ __device__ __forceinline__ void lineSearch(const FmpcBuffers & buf, int iter, co
 }
 } // namespace fmpc
 
-// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
-// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void __launch_bounds__(64) fmpc_line_search_kernel(FmpcBuffers buf, int iter)
 {
-  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax, G = Problem::kIneqDim;
-  using CL = fmpc::CoefLayout<N, M>;
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if(b >= buf.B || buf.status[b] != fmpc::kStatusContinued)
-  {
-    return;
-  }
-  const int T = buf.T;
-  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
-  const double dt = prob.dt();
-  const double t0 = buf.t0[b];
-  const double barrier_eps = buf.barrier_eps[b];
-
-  // merit function at a trial step length: FmpcSolver::calcMeritFunc on variable_ + alpha * delta_variable_ (alpha = 0: the
-  // function part of setupMeritFunc)
-  auto merit = [&](double alpha, double & obj, double & con) {
-    obj = 0;
-    con = 0;
-    typename Problem::StateDimVector x, next_x;
-    NMPC_UNROLL
-    for(int a = 0; a < N; a++)
-    {
-      x[a] = buf.x[fmpc::at(buf, 0, a, N, b)] + alpha * buf.dx[fmpc::at(buf, 0, a, N, b)];
-      con += fabs(buf.x0[static_cast<size_t>(a) * buf.B + b] - x[a]);
-    }
-    for(int i = 0; i < T; i++)
-    {
-      const double t = t0 + i * dt;
-      typename Problem::InputDimVector u;
-      NMPC_UNROLL
-      for(int a = 0; a < M; a++)
-      {
-        u[a] = buf.u[fmpc::at(buf, i, a, M, b)] + alpha * buf.du[fmpc::at(buf, i, a, M, b)];
-      }
-      NMPC_UNROLL
-      for(int a = 0; a < N; a++)
-      {
-        next_x[a] = buf.x[fmpc::at(buf, i + 1, a, N, b)] + alpha * buf.dx[fmpc::at(buf, i + 1, a, N, b)];
-      }
-      obj += prob.runningCost(t, x, u) * dt;
-      const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
-      double logsum = 0, c2 = 0;
-      NMPC_UNROLL
-      for(int j = 0; j < G; j++)
-      {
-        const double sj = buf.s[fmpc::at(buf, i, j, G, b)] + alpha * buf.ds[fmpc::at(buf, i, j, G, b)];
-        logsum += log(sj);
-        c2 += fabs(g[j] + sj);
-      }
-      obj += -1 * barrier_eps * logsum;
-      const typename Problem::StateDimVector f = prob.stateEq(t, x, u);
-      double c1 = 0;
-      NMPC_UNROLL
-      for(int a = 0; a < N; a++)
-      {
-        c1 += fabs(f[a] - next_x[a]);
-      }
-      con += c1;
-      con += c2;
-      x = next_x;
-    }
-    obj += prob.terminalCost(t0 + T * dt, x);
-  };
-
-  // setupMeritFunc: directional derivatives (:852-905)
-  double merit_func_obj, merit_func_const;
-  merit(0.0, merit_func_obj, merit_func_const);
-  double merit_deriv_obj = 0, merit_deriv_const = 0;
-  {
-    double acc = 0;
-    NMPC_UNROLL
-    for(int a = 0; a < N; a++)
-    {
-      const double cf = buf.x0[static_cast<size_t>(a) * buf.B + b] - buf.x[fmpc::at(buf, 0, a, N, b)];
-      acc += fmpcL1RowDeriv(cf, -1 * buf.dx[fmpc::at(buf, 0, a, N, b)]);
-    }
-    merit_deriv_const += acc;
-  }
-  for(int i = 0; i < T; i++)
-  {
-    const double t = t0 + i * dt;
-    typename Problem::StateDimVector x, next_x, dx, dnx;
-    typename Problem::InputDimVector u, du;
-    typename Problem::IneqDimVector s, ds;
-    fmpc::loadVec(buf.x, buf, i, b, x);
-    fmpc::loadVec(buf.x, buf, i + 1, b, next_x);
-    fmpc::loadVec(buf.dx, buf, i, b, dx);
-    fmpc::loadVec(buf.dx, buf, i + 1, b, dnx);
-    fmpc::loadVec(buf.u, buf, i, b, u);
-    fmpc::loadVec(buf.du, buf, i, b, du);
-    fmpc::loadVec(buf.s, buf, i, b, s);
-    fmpc::loadVec(buf.ds, buf, i, b, ds);
-    typename Problem::StateDimVector Lx;
-    typename Problem::InputDimVector Lu;
-    typename Problem::StateStateDimMatrix Lxx;
-    typename Problem::InputInputDimMatrix Luu;
-    typename Problem::StateInputDimMatrix Lxu;
-    prob.calcRunningCostDeriv(t, x, u, Lx, Lu, Lxx, Luu, Lxu);
-    double lx = 0, lu = 0, invdot = 0;
-    NMPC_UNROLL
-    for(int a = 0; a < N; a++)
-    {
-      lx += Lx[a] * dx[a];
-    }
-    NMPC_UNROLL
-    for(int a = 0; a < M; a++)
-    {
-      lu += Lu[a] * du[a];
-    }
-    merit_deriv_obj += (lx + lu) * dt;
-    NMPC_UNROLL
-    for(int j = 0; j < G; j++)
-    {
-      invdot += (1.0 / s[j]) * ds[j];
-    }
-    merit_deriv_obj += -1 * barrier_eps * invdot;
-    {
-      const typename Problem::StateDimVector f = prob.stateEq(t, x, u);
-      double dA = 0, dB = 0, dI = 0;
-      NMPC_UNROLL
-      for(int a = 0; a < N; a++)
-      {
-        const double cf = f[a] - next_x[a];
-        double ra = 0, rb = 0;
-        NMPC_UNROLL
-        for(int r = 0; r < N; r++)
-        {
-          ra += buf.coef[fmpc::at(buf, i, CL::A + a + r * N, CL::kStride, b)] * dx[r];
-        }
-        NMPC_UNROLL
-        for(int r = 0; r < M; r++)
-        {
-          rb += buf.coef[fmpc::at(buf, i, CL::B + a + r * N, CL::kStride, b)] * du[r];
-        }
-        dA += fmpcL1RowDeriv(cf, ra);
-        dB += fmpcL1RowDeriv(cf, rb);
-        dI += fmpcL1RowDeriv(cf, -1 * dnx[a]);
-      }
-      merit_deriv_const += dA;
-      merit_deriv_const += dB;
-      merit_deriv_const += dI;
-    }
-    {
-      typename Problem::IneqStateDimMatrix C;
-      typename Problem::IneqInputDimMatrix D;
-      prob.calcIneqConstDeriv(t, x, u, C, D);
-      const typename Problem::IneqDimVector g = prob.ineqConst(t, x, u);
-      double dC = 0, dD = 0, dI = 0;
-      NMPC_UNROLL
-      for(int j = 0; j < G; j++)
-      {
-        const double cf = g[j] + s[j];
-        double rc = 0, rd = 0;
-        NMPC_UNROLL
-        for(int r = 0; r < N; r++)
-        {
-          rc += C(j, r) * dx[r];
-        }
-        NMPC_UNROLL
-        for(int r = 0; r < M; r++)
-        {
-          rd += D(j, r) * du[r];
-        }
-        dC += fmpcL1RowDeriv(cf, rc);
-        dD += fmpcL1RowDeriv(cf, rd);
-        dI += fmpcL1RowDeriv(cf, ds[j]);
-      }
-      merit_deriv_const += dC;
-      merit_deriv_const += dD;
-      merit_deriv_const += dI;
-    }
-  }
-  {
-    typename Problem::StateDimVector xT, Vx;
-    typename Problem::StateStateDimMatrix Vxx;
-    fmpc::loadVec(buf.x, buf, T, b, xT);
-    prob.calcTerminalCostDeriv(t0 + T * dt, xT, Vx, Vxx);
-    double acc = 0;
-    NMPC_UNROLL
-    for(int a = 0; a < N; a++)
-    {
-      acc += Vx[a] * buf.dx[fmpc::at(buf, T, a, N, b)];
-    }
-    merit_deriv_obj += acc;
-  }
-
-  constexpr double merit_const_scale_min = 1e-3;
-  double merit_const_scale;
-  if(buf.merit_const_scale_from_lagrange_multipliers) // (18.32) in Nocedal & Wright
-  {
-    merit_const_scale = merit_const_scale_min;
-    for(int i = 0; i <= T; i++)
-    {
-      for(int a = 0; a < N; a++)
-      {
-        const double v = fabs(buf.lam[fmpc::at(buf, i, a, N, b)]);
-        merit_const_scale = (merit_const_scale < v) ? v : merit_const_scale;
-      }
-      if(i < T)
-      {
-        for(int j = 0; j < G; j++)
-        {
-          const double v = fabs(buf.nu[fmpc::at(buf, i, j, G, b)]);
-          merit_const_scale = (merit_const_scale < v) ? v : merit_const_scale;
-        }
-      }
-    }
-  }
-  else // (18.33)
-  {
-    constexpr double rho = 0.5;
-    const double v = merit_deriv_obj / ((1.0 - rho) * merit_func_const);
-    merit_const_scale = (v < merit_const_scale_min) ? merit_const_scale_min : v; // std::max(v, min)
-  }
-  const double merit_func = merit_func_obj + merit_const_scale * merit_func_const;
-  const double merit_deriv = merit_deriv_obj + merit_const_scale * merit_deriv_const;
-  buf.merit[0 * buf.B + b] = merit_func;
-  buf.merit[1 * buf.B + b] = merit_deriv;
-  buf.merit[2 * buf.B + b] = merit_const_scale;
-
-  constexpr double armijo_scale = 1e-3;
-  constexpr double alpha_s_update_ratio = 0.5;
-  constexpr double alpha_s_min = 1e-10;
-  double alpha_s = buf.alpha[0 * buf.B + b];
-  while(true)
-  {
-    if(alpha_s < alpha_s_min)
-    {
-      break;
-    }
-    double obj, con;
-    merit(alpha_s, obj, con);
-    const double merit_func_new = obj + merit_const_scale * con;
-    if(merit_func_new < merit_func + armijo_scale * alpha_s * merit_deriv)
-    {
-      break;
-    }
-    alpha_s *= alpha_s_update_ratio;
-  }
-  buf.alpha[2 * buf.B + b] = alpha_s;
-  buf.trace[(static_cast<size_t>(b) * buf.max_iter + (iter - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_ALPHA_S] = alpha_s;
+  fmpc::lineSearch<Problem>(buf, iter, nullptr);
 }
 /** fmpc_line_search_kernel of a problem with time-varying dimensions: every sum over the leading m(i) inputs / g(i) rows. */
 template<class Problem>
@@ -4349,58 +3898,10 @@ __device__ __forceinline__ void plant(const FmpcBuffers & buf, double * x_plant,
 }
 } // namespace fmpc
 
-// (The fixed-dimension kernel keeps its own body: written as a call of the shared dims-aware function it compiles to different
-// instructions — operand order, scheduling — even though every dims guard folds away.)
 template<class Problem>
 __global__ void fmpc_plant_kernel(FmpcBuffers buf, double * x_plant, double * t_plant, double sim_dt, int substeps, int use_feedback)
 {
-  constexpr int N = Problem::kStateDim, M = Problem::kInputDimMax;
-  using GL = fmpc::GainLayout<N, M>;
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if(b >= buf.B)
-  {
-    return;
-  }
-  const Problem prob = fmpc::loadProblem<Problem>(buf, b);
-  typename Problem::StateDimVector x;
-  typename Problem::InputDimVector u0;
-  NMPC_UNROLL
-  for(int a = 0; a < N; a++)
-  {
-    x[a] = x_plant[static_cast<size_t>(a) * buf.B + b];
-  }
-  NMPC_UNROLL
-  for(int a = 0; a < M; a++)
-  {
-    u0[a] = buf.u[fmpc::at(buf, 0, a, M, b)];
-  }
-  double t = t_plant[b];
-  for(int k = 0; k < substeps; k++)
-  {
-    typename Problem::InputDimVector u = u0;
-    if(use_feedback)
-    {
-      NMPC_UNROLL
-      for(int a = 0; a < M; a++)
-      {
-        double acc = 0;
-        NMPC_UNROLL
-        for(int r = 0; r < N; r++)
-        {
-          acc += buf.gain[fmpc::at(buf, 0, GL::K + a + r * M, GL::kStride, b)] * (buf.x[fmpc::at(buf, 0, r, N, b)] - x[r]);
-        }
-        u[a] += acc;
-      }
-    }
-    x = prob.stateEq(t, x, u, sim_dt);
-    t += sim_dt;
-  }
-  NMPC_UNROLL
-  for(int a = 0; a < N; a++)
-  {
-    x_plant[static_cast<size_t>(a) * buf.B + b] = x[a];
-  }
-  t_plant[b] = t;
+  fmpc::plant<Problem>(buf, x_plant, t_plant, sim_dt, substeps, use_feedback, nullptr);
 }
 template<class Problem>
 __global__ void fmpc_plant_dims_kernel(FmpcBuffers buf, const int * dims, double * x_plant, double * t_plant, double sim_dt, int substeps,

@@ -80,8 +80,11 @@ dim3 fmpcTransposeGrid(int B, int steps, int E, int to_device)
 }
 
 /** One row of the closed-loop log (nmpc_hip_fmpc_mpc_run): state handed to the solve, first input, status, iterations and
-    the KKT error of the last iteration.  Logs are [tick][element][instance] on the device. */
-__global__ void fmpc_log_kernel(FmpcBuffers buf, int tick, double * x_log, double * u0_log, int * status_log, int * iter_log, double * kkt_log)
+    the KKT error of the last iteration.  Logs are [tick][element][instance] on the device.  With time-varying dimensions (kDims)
+    u0_log entries beyond m(0) of the tick's solve are 0. */
+template<bool kDims>
+__device__ __forceinline__ void logRow(const FmpcBuffers & buf, const int * dims, int tick, double * x_log, double * u0_log, int * status_log,
+                                       int * iter_log, double * kkt_log)
 {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if(b >= buf.B)
@@ -92,31 +95,11 @@ __global__ void fmpc_log_kernel(FmpcBuffers buf, int tick, double * x_log, doubl
   {
     x_log[(static_cast<size_t>(tick) * buf.N + a) * buf.B + b] = buf.x0[static_cast<size_t>(a) * buf.B + b];
   }
-  for(int a = 0; a < buf.M; a++)
+  int m0 = buf.M;
+  if constexpr(kDims)
   {
-    u0_log[(static_cast<size_t>(tick) * buf.M + a) * buf.B + b] = buf.u[static_cast<size_t>(a) * buf.B + b];
+    m0 = dims[b];
   }
-  const int it = buf.iters[b];
-  status_log[static_cast<size_t>(tick) * buf.B + b] = buf.status[b];
-  iter_log[static_cast<size_t>(tick) * buf.B + b] = it;
-  kkt_log[static_cast<size_t>(tick) * buf.B + b] =
-      it > 0 ? buf.trace[(static_cast<size_t>(b) * buf.max_iter + (it - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_KKT_ERROR] : 0.0;
-}
-
-/** fmpc_log_kernel of a problem with time-varying dimensions: u0_log entries beyond m(0) of the tick's solve are 0. */
-__global__ void fmpc_log_dims_kernel(FmpcBuffers buf, const int * dims, int tick, double * x_log, double * u0_log, int * status_log, int * iter_log,
-                                     double * kkt_log)
-{
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if(b >= buf.B)
-  {
-    return;
-  }
-  for(int a = 0; a < buf.N; a++)
-  {
-    x_log[(static_cast<size_t>(tick) * buf.N + a) * buf.B + b] = buf.x0[static_cast<size_t>(a) * buf.B + b];
-  }
-  const int m0 = dims[b];
   for(int a = 0; a < buf.M; a++)
   {
     u0_log[(static_cast<size_t>(tick) * buf.M + a) * buf.B + b] = a < m0 ? buf.u[static_cast<size_t>(a) * buf.B + b] : 0.0;
@@ -126,6 +109,15 @@ __global__ void fmpc_log_dims_kernel(FmpcBuffers buf, const int * dims, int tick
   iter_log[static_cast<size_t>(tick) * buf.B + b] = it;
   kkt_log[static_cast<size_t>(tick) * buf.B + b] =
       it > 0 ? buf.trace[(static_cast<size_t>(b) * buf.max_iter + (it - 1)) * NMPC_HIP_FMPC_NTRACE + NMPC_HIP_FMPC_TRACE_KKT_ERROR] : 0.0;
+}
+__global__ void fmpc_log_kernel(FmpcBuffers buf, int tick, double * x_log, double * u0_log, int * status_log, int * iter_log, double * kkt_log)
+{
+  logRow<false>(buf, nullptr, tick, x_log, u0_log, status_log, iter_log, kkt_log);
+}
+__global__ void fmpc_log_dims_kernel(FmpcBuffers buf, const int * dims, int tick, double * x_log, double * u0_log, int * status_log, int * iter_log,
+                                     double * kkt_log)
+{
+  logRow<true>(buf, dims, tick, x_log, u0_log, status_log, iter_log, kkt_log);
 }
 
 __global__ void fmpc_fill_kernel(double * p, size_t n, double v)
