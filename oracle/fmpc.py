@@ -78,7 +78,7 @@ def _ip(a):
 
 
 def model_info(model: str):
-    """(state_dim, input_dim, ineq_dim, number of parameter doubles)."""
+    """(state_dim, input_dim, ineq_dim, number of parameter doubles); the two dimensions are capacities where dims_at varies."""
     n, m, g, p = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     rc = lib().oracle_fmpc_model_info(model.encode(), C.byref(n), C.byref(m), C.byref(g), C.byref(p))
     if rc != 0:
@@ -90,6 +90,15 @@ def default_params(model: str) -> np.ndarray:
     out = np.zeros(model_info(model)[3])
     assert lib().oracle_fmpc_default_params(model.encode(), _dp(out)) == 0
     return out
+
+
+def dims_at(model: str, t: float, params=None):
+    """(input_dim, ineq_dim) of a step at time t."""
+    m, g = C.c_int(), C.c_int()
+    p = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
+    if lib().oracle_fmpc_dims_at(model.encode(), _dp(p), C.c_double(t), C.byref(m), C.byref(g)) != 0:
+        raise ValueError(f"unknown FMPC oracle model {model!r}")
+    return m.value, g.value
 
 
 @dataclass
@@ -196,6 +205,90 @@ def solve_batch(model: str, cfg: FmpcConfig, params, current_t, current_x, var: 
                                                       _ip(status), _ip(iters), _dp(trace), _dp(K0), int(n_threads))
     assert rc == 0, rc
     return BatchResult(status, iters, v, be, trace, np.transpose(K0, (0, 2, 1)).copy())
+
+
+def _batch_args(model, cfg, params, current_t, current_x, var, barrier_eps):
+    """The leading arguments the batched entry points share, the arrays they point into (to be kept alive over the call), and the
+    copies of the variable and barrier_eps that the call updates in place."""
+    n, m, g, pd = model_info(model)
+    T = cfg.horizon_steps
+    x0 = np.ascontiguousarray(current_x, dtype=np.float64)
+    B = x0.shape[0]
+    v = Variable(*(np.ascontiguousarray(a, dtype=np.float64).copy() for a in var.arrays()))
+    assert v.x.shape == (B, T + 1, n) and v.u.shape == (B, T, m) and v.s.shape == (B, T, g)
+    p = None if params is None else np.ascontiguousarray(params, dtype=np.float64)
+    per_instance = int(p is not None and p.ndim == 2)
+    if per_instance:
+        assert p.shape == (B, pd)
+    t0 = np.ascontiguousarray(np.broadcast_to(0.0 if current_t is None else current_t, (B,)), dtype=np.float64)
+    be = np.array(np.broadcast_to(1e-4 if barrier_eps is None else barrier_eps, (B,)), dtype=np.float64)
+    args = (model.encode(), C.byref(cfg), _dp(p), per_instance, B, _dp(t0), _dp(x0), _dp(v.x), _dp(v.u), _dp(v.lam), _dp(v.s),
+            _dp(v.nu), _dp(be))
+    return args, (t0, x0, p), v, be
+
+
+@dataclass
+class FullBatchResult:
+    status: np.ndarray
+    iters: np.ndarray
+    variable: Variable
+    barrier_eps: np.ndarray
+    trace: np.ndarray  # [B][max_iter][NTRACE]
+    k: np.ndarray  # [B][T][M], 0 beyond a step's input dimension
+    K: np.ndarray  # [B][T][M][N], rows beyond a step's input dimension 0
+    s: np.ndarray  # [B][T+1][N]
+    P: np.ndarray  # [B][T+1][N][N]
+    delta: Variable  # of the last iteration that reached the forward pass, 0 beyond a step's dimensions
+    merit: np.ndarray  # [B][3]: merit_func_, merit_deriv_, merit_const_scale_ of the last line search
+
+
+def solve_batch_full(model: str, cfg: FmpcConfig, params, current_t, current_x, var: Variable, barrier_eps=None,
+                     n_threads: int = 16) -> FullBatchResult:
+    """solve_batch with every intermediate solve() returns, for each instance."""
+    n, m, g, _ = model_info(model)
+    T = cfg.horizon_steps
+    args, keep, v, be = _batch_args(model, cfg, params, current_t, current_x, var, barrier_eps)
+    B = len(be)
+    status, iters = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    trace = np.zeros((B, cfg.max_iter, NTRACE))
+    gk, gK, gs, gP = np.zeros((B, T, m)), np.zeros((B, T, n, m)), np.zeros((B, T + 1, n)), np.zeros((B, T + 1, n, n))
+    shapes = ((T + 1, n), (T, m), (T + 1, n), (T, g), (T, g))
+    delta = np.zeros((B, sum(int(np.prod(sh)) for sh in shapes)))
+    merit = np.zeros((B, 3))
+    rc = lib().oracle_fmpc_solve_batch_full(*args, _ip(status), _ip(iters), _dp(trace), _dp(gk), _dp(gK), _dp(gs), _dp(gP),
+                                            _dp(delta), _dp(merit), int(n_threads))
+    assert rc == 0, rc
+    parts, o = [], 0
+    for sh in shapes:
+        size = int(np.prod(sh))
+        parts.append(delta[:, o:o + size].reshape((B,) + sh).copy())
+        o += size
+    return FullBatchResult(status, iters, v, be, trace, gk, np.transpose(gK, (0, 1, 3, 2)).copy(), gs,
+                           np.transpose(gP, (0, 1, 3, 2)).copy(), Variable(*parts), merit)
+
+
+@dataclass
+class ClosedLoopResult:
+    variable: Variable  # after the last tick
+    barrier_eps: np.ndarray
+    x_log: np.ndarray  # [B][n_ticks][N]: the state each tick's solve started from
+    u0_log: np.ndarray  # [B][n_ticks][M]: u_list[0] of each tick, 0 beyond the step's input dimension
+    status_log: np.ndarray
+    iter_log: np.ndarray
+
+
+def closed_loop(model: str, cfg: FmpcConfig, params, current_t, current_x, var: Variable, n_ticks: int, sim_dt: float,
+                substeps: int = 1, barrier_eps=None, n_threads: int = 16) -> ClosedLoopResult:
+    """n_ticks times { solve from the variable of the tick before; `substeps` plant steps stateEq(t, x, u_list[0], sim_dt) }."""
+    n, m, _, _ = model_info(model)
+    args, keep, v, be = _batch_args(model, cfg, params, current_t, current_x, var, barrier_eps)
+    B = len(be)
+    x_log, u0_log = np.zeros((B, n_ticks, n)), np.zeros((B, n_ticks, m))
+    status_log, iter_log = np.zeros((B, n_ticks), dtype=np.int32), np.zeros((B, n_ticks), dtype=np.int32)
+    rc = lib().oracle_fmpc_closed_loop(*args, int(n_ticks), C.c_double(sim_dt), int(substeps), _dp(x_log), _dp(u0_log),
+                                       _ip(status_log), _ip(iter_log), int(n_threads))
+    assert rc == 0, rc
+    return ClosedLoopResult(v, be, x_log, u0_log, status_log, iter_log)
 
 
 def evaluate(model: str, params, t: float, x, u, step_dt: float = 0.0) -> dict:

@@ -1,8 +1,9 @@
 // TEST INFRASTRUCTURE — NOT PRODUCT CODE (see oracle/fmpc_oracle.hpp header).
 //
 // ctypes-loadable C entry points over the CPU FMPC oracle: single solve (with every intermediate the parity tests compare),
-// threaded batch solve (also the cpu_baseline leg of bench.py --workload fmpc, kind "port"), model evaluation, the LDLT
-// restatement and l1NormDirectionalDeriv.
+// threaded batch solve (also the cpu_baseline leg of bench.py --workload fmpc, kind "port") with or without those
+// intermediates, the closed loop solve -> plant step, model evaluation, a step's dimensions, the LDLT restatement and
+// l1NormDirectionalDeriv.
 #include "fmpc_models.hpp"
 #include "fmpc_oracle.hpp"
 
@@ -33,6 +34,10 @@ int dispatch(const char * name, F && f)
   {
     return f(PointMass());
   }
+  if(s == Vertical::kName)
+  {
+    return f(Vertical());
+  }
   return -100;
 }
 
@@ -47,6 +52,76 @@ M fromParams(const double * params)
     std::memcpy(static_cast<void *>(&m), params, sizeof(M));
   }
   return m;
+}
+
+/** Problem object of instance b: one shared parameter blob, or one per instance. */
+template<class M>
+M fromParams(const double * params, int per_instance_params, int b)
+{
+  return fromParams<M>(params && per_instance_params ? params + static_cast<size_t>(b) * (sizeof(M) / sizeof(double)) : params);
+}
+
+/** p + n, or NULL for an output the caller does not want. */
+template<class T>
+T * off(T * p, size_t n)
+{
+  return p ? p + n : nullptr;
+}
+
+/** fn(b) for every b < batch on n_threads CPU threads (dynamic chunks, threads pinned to the allowed CPUs in order). */
+template<class Fn>
+void parallelFor(int batch, int n_threads, Fn && fn)
+{
+  std::atomic<int> next(0);
+  const int chunk = std::max(1, std::min(16, batch / std::max(1, n_threads * 8)));
+  cpu_set_t allowed;
+  CPU_ZERO(&allowed);
+  sched_getaffinity(0, sizeof(allowed), &allowed);
+  std::vector<int> cpus;
+  for(int i = 0; i < CPU_SETSIZE; i++)
+  {
+    if(CPU_ISSET(i, &allowed))
+    {
+      cpus.push_back(i);
+    }
+  }
+  auto work = [&](int tid) {
+    if(n_threads > 1 && !cpus.empty())
+    {
+      cpu_set_t one;
+      CPU_ZERO(&one);
+      CPU_SET(cpus[tid % cpus.size()], &one);
+      pthread_setaffinity_np(pthread_self(), sizeof(one), &one);
+    }
+    for(;;)
+    {
+      const int b0 = next.fetch_add(chunk);
+      if(b0 >= batch)
+      {
+        break;
+      }
+      for(int b = b0; b < std::min(batch, b0 + chunk); b++)
+      {
+        fn(b);
+      }
+    }
+  };
+  if(n_threads <= 1)
+  {
+    work(0);
+  }
+  else
+  {
+    std::vector<std::thread> th;
+    for(int i = 0; i < n_threads; i++)
+    {
+      th.emplace_back(work, i);
+    }
+    for(auto & t : th)
+    {
+      t.join();
+    }
+  }
 }
 } // namespace
 
@@ -103,6 +178,21 @@ extern "C"
       return 0;
     });
   }
+
+  /** Input and inequality dimension of a step at time t: (m, g) of oracle_fmpc_model_info unless the model's vary with time. */
+  int oracle_fmpc_dims_at(const char * model, const double * params, double t, int * m, int * g)
+  {
+    return dispatch(model, [&](auto mdl) {
+      using M = decltype(mdl);
+      *m = M::M;
+      *g = M::G;
+      if constexpr(HasStepDims<M>::value)
+      {
+        fromParams<M>(params).dims(t, *m, *g);
+      }
+      return 0;
+    });
+  }
 }
 
 namespace
@@ -142,7 +232,8 @@ int solveOne(const M & mdl,
              double * gain_K,
              double * gain_s,
              double * gain_P,
-             double * delta)
+             double * delta,
+             double * merit)
 {
   const int T = cfg.horizon_steps;
   constexpr int N = M::N, MM = M::M, G = M::G;
@@ -150,11 +241,11 @@ int solveOne(const M & mdl,
   solver.config() = cfg;
   solver.barrierEps() = *barrier_eps;
   Variable v(T, N, MM, G);
-  std::copy(x, x + (T + 1) * N, v.x.begin());
-  std::copy(u, u + T * MM, v.u.begin());
-  std::copy(lambda, lambda + (T + 1) * N, v.lambda.begin());
-  std::copy(s, s + T * G, v.s.begin());
-  std::copy(nu, nu + T * G, v.nu.begin());
+  std::copy(x, x + v.x.size(), v.x.begin());
+  std::copy(u, u + v.u.size(), v.u.begin());
+  std::copy(lambda, lambda + v.lambda.size(), v.lambda.begin());
+  std::copy(s, s + v.s.size(), v.s.begin());
+  std::copy(nu, nu + v.nu.size(), v.nu.begin());
   int status;
   try
   {
@@ -229,6 +320,12 @@ int solveOne(const M & mdl,
       p = std::copy(vec->begin(), vec->end(), p);
     }
   }
+  if(merit) // of the last iteration that set up the line search
+  {
+    merit[0] = solver.meritFunc();
+    merit[1] = solver.meritDeriv();
+    merit[2] = solver.meritConstScale();
+  }
   return status;
 }
 } // namespace
@@ -258,7 +355,7 @@ extern "C"
     return dispatch(model, [&](auto mdl) {
       using M = decltype(mdl);
       return solveOne(fromParams<M>(params), toConfig(c), current_t, current_x, x, u, lambda, s, nu, barrier_eps, iters, trace,
-                      gain_k, gain_K, gain_s, gain_P, delta);
+                      gain_k, gain_K, gain_s, gain_P, delta, nullptr);
     });
   }
 
@@ -289,69 +386,128 @@ extern "C"
       using M = decltype(mdl0);
       constexpr int N = M::N, MM = M::M, G = M::G;
       const Config cfg = toConfig(c);
-      const int T = cfg.horizon_steps;
-      const int pd = static_cast<int>(sizeof(M) / sizeof(double));
-      std::atomic<int> next(0);
-      const int chunk = std::max(1, std::min(16, batch / std::max(1, n_threads * 8)));
-      cpu_set_t allowed;
-      CPU_ZERO(&allowed);
-      sched_getaffinity(0, sizeof(allowed), &allowed);
-      std::vector<int> cpus;
-      for(int i = 0; i < CPU_SETSIZE; i++)
-      {
-        if(CPU_ISSET(i, &allowed))
+      const size_t T = cfg.horizon_steps;
+      parallelFor(batch, n_threads, [&](size_t b) {
+        std::vector<double> K(gain_K0 ? T * MM * N : 0);
+        status[b] = solveOne(fromParams<M>(params, per_instance_params, b), cfg, current_t ? current_t[b] : 0.0, current_x + b * N,
+                             x + b * (T + 1) * N, u + b * T * MM, lambda + b * (T + 1) * N, s + b * T * G, nu + b * T * G,
+                             barrier_eps + b, off(iters, b), off(trace, b * cfg.max_iter * ORACLE_FMPC_NTRACE), nullptr,
+                             gain_K0 ? K.data() : nullptr, nullptr, nullptr, nullptr, nullptr);
+        if(gain_K0)
         {
-          cpus.push_back(i);
+          std::copy(K.begin(), K.begin() + MM * N, gain_K0 + b * MM * N);
         }
-      }
-      auto work = [&](int tid) {
-        if(n_threads > 1 && !cpus.empty())
+      });
+      return 0;
+    });
+  }
+
+  /** oracle_fmpc_solve_batch with the optional outputs of oracle_fmpc_solve for every instance: gain_k [B][T][M], gain_K
+      [B][T][M*N], gain_s [B][T+1][N], gain_P [B][T+1][N*N], delta [B][2 (T+1) N + T M + 2 T G] and merit [B][3] (merit_func_,
+      merit_deriv_, merit_const_scale_).  Any of them, iters and trace may be NULL. */
+  int oracle_fmpc_solve_batch_full(const char * model,
+                                   const oracle_fmpc_config * c,
+                                   const double * params,
+                                   int per_instance_params,
+                                   int batch,
+                                   const double * current_t,
+                                   const double * current_x,
+                                   double * x,
+                                   double * u,
+                                   double * lambda,
+                                   double * s,
+                                   double * nu,
+                                   double * barrier_eps,
+                                   int * status,
+                                   int * iters,
+                                   double * trace,
+                                   double * gain_k,
+                                   double * gain_K,
+                                   double * gain_s,
+                                   double * gain_P,
+                                   double * delta,
+                                   double * merit,
+                                   int n_threads)
+  {
+    return dispatch(model, [&](auto mdl0) {
+      using M = decltype(mdl0);
+      constexpr int N = M::N, MM = M::M, G = M::G;
+      const Config cfg = toConfig(c);
+      const size_t T = cfg.horizon_steps;
+      parallelFor(batch, n_threads, [&](size_t b) {
+        status[b] = solveOne(fromParams<M>(params, per_instance_params, b), cfg, current_t[b], current_x + b * N, x + b * (T + 1) * N,
+                             u + b * T * MM, lambda + b * (T + 1) * N, s + b * T * G, nu + b * T * G, barrier_eps + b, off(iters, b),
+                             off(trace, b * cfg.max_iter * ORACLE_FMPC_NTRACE), off(gain_k, b * T * MM), off(gain_K, b * T * MM * N),
+                             off(gain_s, b * (T + 1) * N), off(gain_P, b * (T + 1) * N * N),
+                             off(delta, b * (2 * (T + 1) * N + T * MM + 2 * T * G)), off(merit, b * 3));
+      });
+      return 0;
+    });
+  }
+
+  /** Closed loop of every instance: n_ticks times { log x; solve(t, x) from the variable of the tick before (barrier parameter
+      carried); log u_list[0] (0 beyond the step's input dimension), status and iteration count; `substeps` plant steps
+      x <- stateEq(t, x, u_list[0], sim_dt), the input keeping the size it has at the tick's time }.  Variable in / out;
+      logs [B][n_ticks][...]. */
+  int oracle_fmpc_closed_loop(const char * model,
+                              const oracle_fmpc_config * c,
+                              const double * params,
+                              int per_instance_params,
+                              int batch,
+                              const double * current_t,
+                              const double * current_x,
+                              double * x,
+                              double * u,
+                              double * lambda,
+                              double * s,
+                              double * nu,
+                              double * barrier_eps,
+                              int n_ticks,
+                              double sim_dt,
+                              int substeps,
+                              double * x_log,
+                              double * u0_log,
+                              int * status_log,
+                              int * iter_log,
+                              int n_threads)
+  {
+    return dispatch(model, [&](auto mdl0) {
+      using M = decltype(mdl0);
+      constexpr int N = M::N, MM = M::M, G = M::G;
+      const Config cfg = toConfig(c);
+      const size_t T = cfg.horizon_steps;
+      parallelFor(batch, n_threads, [&](size_t b) {
+        const M mdl = fromParams<M>(params, per_instance_params, b);
+        double t = current_t[b], xt[N];
+        std::copy(current_x + b * N, current_x + (b + 1) * N, xt);
+        double * u0 = u + b * T * MM;
+        for(int k = 0; k < n_ticks; k++)
         {
-          cpu_set_t one;
-          CPU_ZERO(&one);
-          CPU_SET(cpus[tid % cpus.size()], &one);
-          pthread_setaffinity_np(pthread_self(), sizeof(one), &one);
-        }
-        std::vector<double> K(static_cast<size_t>(T) * MM * N);
-        for(;;)
-        {
-          const int b0 = next.fetch_add(chunk);
-          if(b0 >= batch)
+          const size_t row = b * n_ticks + k;
+          std::copy(xt, xt + N, x_log + row * N);
+          iter_log[row] = 0;
+          status_log[row] = solveOne(mdl, cfg, t, xt, x + b * (T + 1) * N, u0, lambda + b * (T + 1) * N, s + b * T * G,
+                                     nu + b * T * G, barrier_eps + b, iter_log + row, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr);
+          int m0 = MM, g0 = G;
+          if constexpr(HasStepDims<M>::value)
           {
-            break;
+            mdl.dims(t, m0, g0);
           }
-          for(int b = b0; b < std::min(batch, b0 + chunk); b++)
+          for(int a = 0; a < MM; a++)
           {
-            const M mdl = fromParams<M>(params ? params + (per_instance_params ? static_cast<size_t>(b) * pd : 0) : nullptr);
-            status[b] = solveOne(mdl, cfg, current_t ? current_t[b] : 0.0, current_x + static_cast<size_t>(b) * N,
-                                 x + static_cast<size_t>(b) * (T + 1) * N, u + static_cast<size_t>(b) * T * MM,
-                                 lambda + static_cast<size_t>(b) * (T + 1) * N, s + static_cast<size_t>(b) * T * G,
-                                 nu + static_cast<size_t>(b) * T * G, barrier_eps + b, iters ? iters + b : nullptr,
-                                 trace ? trace + static_cast<size_t>(b) * cfg.max_iter * ORACLE_FMPC_NTRACE : nullptr, nullptr,
-                                 gain_K0 ? K.data() : nullptr, nullptr, nullptr, nullptr);
-            if(gain_K0)
-            {
-              std::copy(K.begin(), K.begin() + MM * N, gain_K0 + static_cast<size_t>(b) * MM * N);
-            }
+            u0_log[row * MM + a] = a < m0 ? u0[a] : 0.0;
+          }
+          const double tick_t = t;
+          for(int sub = 0; sub < substeps; sub++)
+          {
+            double next[N];
+            mdl.stateEqDt(tick_t, xt, u0, sim_dt, next);
+            std::copy(next, next + N, xt);
+            t += sim_dt;
           }
         }
-      };
-      if(n_threads <= 1)
-      {
-        work(0);
-      }
-      else
-      {
-        std::vector<std::thread> th;
-        for(int i = 0; i < n_threads; i++)
-        {
-          th.emplace_back(work, i);
-        }
-        for(auto & t : th)
-        {
-          t.join();
-        }
-      }
+      });
       return 0;
     });
   }
@@ -424,7 +580,7 @@ extern "C"
 
   double oracle_fmpc_l1_dir_deriv(const double * func, const double * jac, const double * dir, int out_dim, int in_dim)
   {
-    return l1NormDirectionalDeriv(func, jac, dir, out_dim, in_dim);
+    return l1NormDirectionalDeriv(func, jac, out_dim, dir, out_dim, in_dim);
   }
 
   /** x = G^-1 b through the LDLT restatement (b: n x c column-major, in place).  Returns 1 if info() == Success. */

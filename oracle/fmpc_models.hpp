@@ -3,8 +3,10 @@
 // The two problems the reference's FMPC tests define, restated on flat column-major arrays:
 //   Oscillator   FmpcProblemOscillator  nmpc_fmpc/tests/src/TestFmpcOscillator.cpp:18-135 (Van der Pol, n=2 m=1 g=3)
 //   CartPole     FmpcProblemCartPole    nmpc_fmpc/tests/src/TestFmpcCartPole.cpp:32-267   (n=4 m=1 g=4)
-// plus one problem of this repo with two inputs (so that the pivoted LDLT of G is exercised beyond 1 x 1):
-//   PointMass    planar point mass with velocity-dependent drag, n=4 m=2 g=4 (no reference counterpart)
+// plus two problems of this repo (no reference counterpart):
+//   PointMass    planar point mass with velocity-dependent drag, n=4 m=2 g=4: two inputs, so that the pivoted LDLT of G is
+//                exercised beyond 1 x 1
+//   Vertical     vertical motion under a contact schedule, n=2 m(t) in {0, 1, 2} g(t) = 2 m(t): time-varying dimensions
 #pragma once
 
 #include <cmath>
@@ -358,6 +360,143 @@ struct PointMass
     D[1 + 0 * 4] = 1;
     D[2 + 1 * 4] = -1;
     D[3 + 1 * 4] = 1;
+  }
+};
+
+/** fmpc_vertical (include/nmpc_amd/models/FmpcVerticalMotion.hpp) restated: state [z, vz], one force per contact, rows
+    f_min - f_j <= 0, f_j - f_max <= 0.  M and G are capacities: dims(t) gives the step's dimensions, every method sizes u and its
+    outputs by them, with the capacities as leading dimensions.  Same memory image as the library's problem object (14 doubles). */
+struct Vertical
+{
+  static constexpr int N = 2, M = 2, G = 4;
+  static constexpr const char * kName = "fmpc_vertical";
+  static constexpr double g_ = 9.80665;
+  double dt = 0.01;
+  double running_x[2] = {1.0, 1e-3};
+  double running_u = 1e-3;
+  double terminal_x[2] = {1.0, 1e-3};
+  double mass = 1.0, f_min = 0.0, f_max = 30.0, ref_switch_t = 8.0;
+  double ds_begin = 2.0, ds_end = 3.0, fl_begin = 4.5, fl_end = 5.0;
+
+  /** Contacts at t; the offset makes a t0 + i dt that rounds to a hair before a switch count as after it. */
+  int inputDim(double t) const
+  {
+    t += 1e-6;
+    if(ds_begin < t && t < ds_end)
+    {
+      return 2;
+    }
+    if(fl_begin < t && t < fl_end)
+    {
+      return 0;
+    }
+    return 1;
+  }
+  void dims(double t, int & m, int & g) const
+  {
+    m = inputDim(t);
+    g = 2 * m;
+  }
+  double refPos(double t) const
+  {
+    t += 1e-6;
+    return (t < ref_switch_t) ? 1.0 : 0.0;
+  }
+  void stateEqDt(double t, const double * x, const double * u, double step, double * out) const
+  {
+    const int m = inputDim(t);
+    double force = 0;
+    for(int j = 0; j < m; j++)
+    {
+      force += u[j];
+    }
+    out[0] = x[0] + step * x[1];
+    out[1] = x[1] + step * (force / mass - g_);
+  }
+  void stateEq(double t, const double * x, const double * u, double * out) const
+  {
+    stateEqDt(t, x, u, dt, out);
+  }
+  double runningCost(double t, const double * x, const double * u) const
+  {
+    const int m = inputDim(t);
+    const double e0 = x[0] - refPos(t), e1 = x[1];
+    double uu = 0;
+    for(int j = 0; j < m; j++)
+    {
+      uu += u[j] * u[j];
+    }
+    return 0.5 * (running_x[0] * (e0 * e0) + running_x[1] * (e1 * e1)) + 0.5 * running_u * uu;
+  }
+  double terminalCost(double t, const double * x) const
+  {
+    const double e0 = x[0] - refPos(t), e1 = x[1];
+    return 0.5 * (terminal_x[0] * (e0 * e0) + terminal_x[1] * (e1 * e1));
+  }
+  void ineqConst(double t, const double *, const double * u, double * g) const
+  {
+    const int m = inputDim(t);
+    for(int j = 0; j < m; j++)
+    {
+      g[2 * j] = f_min - u[j];
+      g[2 * j + 1] = u[j] - f_max;
+    }
+  }
+  void calcStateEqDeriv(double t, const double *, const double *, double * A, double * B) const
+  {
+    const int m = inputDim(t);
+    A[0] = 1;
+    A[1] = 0;
+    A[2] = dt;
+    A[3] = 1;
+    for(int j = 0; j < m; j++)
+    {
+      B[0 + 2 * j] = 0;
+      B[1 + 2 * j] = (1.0 / mass) * dt;
+    }
+  }
+  void calcRunningCostDeriv(double t, const double * x, const double * u, double * Lx, double * Lu, double * Lxx, double * Luu,
+                            double * Lxu) const
+  {
+    const int m = inputDim(t);
+    Lx[0] = running_x[0] * (x[0] - refPos(t));
+    Lx[1] = running_x[1] * x[1];
+    Lxx[0] = running_x[0];
+    Lxx[1] = 0;
+    Lxx[2] = 0;
+    Lxx[3] = running_x[1];
+    for(int j = 0; j < m; j++)
+    {
+      Lu[j] = running_u * u[j];
+      Lxu[0 + 2 * j] = 0;
+      Lxu[1 + 2 * j] = 0;
+      for(int k = 0; k < m; k++)
+      {
+        Luu[k + j * M] = (j == k) ? running_u : 0.0;
+      }
+    }
+  }
+  void calcTerminalCostDeriv(double t, const double * x, double * Lx, double * Lxx) const
+  {
+    Lx[0] = terminal_x[0] * (x[0] - refPos(t));
+    Lx[1] = terminal_x[1] * x[1];
+    Lxx[0] = terminal_x[0];
+    Lxx[1] = 0;
+    Lxx[2] = 0;
+    Lxx[3] = terminal_x[1];
+  }
+  void calcIneqConstDeriv(double t, const double *, const double *, double * C, double * D) const
+  {
+    const int m = inputDim(t);
+    for(int r = 0; r < 2 * m; r++)
+    {
+      C[r + 0 * G] = 0;
+      C[r + 1 * G] = 0;
+      for(int j = 0; j < m; j++)
+      {
+        D[r + j * G] = (r == 2 * j) ? -1.0 : ((r == 2 * j + 1) ? 1.0 : 0.0);
+      }
+    }
   }
 };
 } // namespace oracle_fmpc

@@ -33,8 +33,11 @@
 // followed by a non-zero one; that branch (FullPivLU fallback, :588-602) is restated as a full-pivot Gaussian elimination.
 // Reductions are summed in ascending index order (Eigen's order is implementation-defined; tolerance + exact statuses /
 // iteration counts is the parity target, as for the DDP oracle).
-// Fixed dimensions only (the reference's Eigen::Dynamic InputDim / IneqDim, FmpcSolver.hpp:211-218, is not restated: neither
-// of its tests uses it).
+// Time-varying dimensions (the reference's Eigen::Dynamic InputDim / IneqDim, FmpcSolver.hpp:211-218): a model with a method
+// `void dims(double t, int & m, int & g) const` sizes step i of the horizon by dims(current_t + i dt), evaluated once per solve;
+// Model::M and Model::G are then capacities.  Variables, deltas and coefficient records stay padded to the capacities, which are
+// also every leading dimension; the variable's entries beyond a step's dimensions are neither read nor written, and k, K and
+// the deltas there are 0.  A model without that method has m(i) = M, g(i) = G as compile-time constants.
 #pragma once
 
 #include <algorithm>
@@ -43,12 +46,13 @@
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace oracle_fmpc
 {
-/** l1NormDirectionalDeriv (MathUtils.h:17-38): jac is (out_dim x in_dim) column-major. */
-inline double l1NormDirectionalDeriv(const double * func, const double * jac, const double * dir, int out_dim, int in_dim)
+/** l1NormDirectionalDeriv (MathUtils.h:17-38): jac is (out_dim x in_dim) column-major with leading dimension ld. */
+inline double l1NormDirectionalDeriv(const double * func, const double * jac, int ld, const double * dir, int out_dim, int in_dim)
 {
   double deriv = 0.0;
   for(int i = 0; i < out_dim; i++)
@@ -56,7 +60,7 @@ inline double l1NormDirectionalDeriv(const double * func, const double * jac, co
     double d = 0;
     for(int j = 0; j < in_dim; j++)
     {
-      d += jac[i + j * out_dim] * dir[j];
+      d += jac[i + j * ld] * dir[j];
     }
     if(func[i] > 0)
     {
@@ -406,6 +410,22 @@ struct TraceRow
   double alpha_s = 0;
 };
 
+/** Input and inequality dimension of one step of the horizon. */
+struct StepDims
+{
+  int m, g;
+};
+
+/** Whether Model has time-varying dimensions, i.e. a method dims(t, m, g). */
+template<class Model, class = void>
+struct HasStepDims : std::false_type
+{
+};
+template<class Model>
+struct HasStepDims<Model, std::void_t<decltype(&Model::dims)>> : std::true_type
+{
+};
+
 /** nmpc_fmpc::FmpcSolver<N, M, G> on flat column-major arrays. */
 template<class Model>
 class FmpcSolver
@@ -414,6 +434,7 @@ public:
   static constexpr int N = Model::N;
   static constexpr int M = Model::M;
   static constexpr int G = Model::G;
+  static constexpr bool kStepDims = HasStepDims<Model>::value;
 
   /** Coefficient (FmpcSolver.h:161-230); all matrices column-major. */
   struct Coefficient
@@ -478,6 +499,19 @@ public:
   {
     return problem_;
   }
+  /** Dimensions of step i of the last solve: the compile-time {M, G} for a fixed-dimension model, so that every loop bound
+      below folds to a constant there. */
+  StepDims stepDims(int i) const
+  {
+    if constexpr(kStepDims)
+    {
+      return step_dims_[i];
+    }
+    else
+    {
+      return {M, G};
+    }
+  }
 
   /** FmpcSolver::solve (FmpcSolver.hpp:156-255). */
   Status solve(double current_t, const double * current_x, const Variable & initial_variable)
@@ -486,6 +520,14 @@ public:
     current_t_ = current_t;
     std::copy(current_x, current_x + N, current_x_);
     variable_ = initial_variable;
+    if constexpr(kStepDims)
+    {
+      step_dims_.resize(T);
+      for(int i = 0; i < T; i++)
+      {
+        problem_.dims(current_t_ + i * problem_.dt, step_dims_[i].m, step_dims_[i].g);
+      }
+    }
 
     if(config_.init_complementary_variable) // :170-187
     {
@@ -498,7 +540,7 @@ public:
         const double t = current_t_ + i * problem_.dt;
         double g[G > 0 ? G : 1];
         problem_.ineqConst(t, &variable_.x[i * N], &variable_.u[i * M], g);
-        for(int j = 0; j < G; j++)
+        for(int j = 0; j < stepDims(i).g; j++)
         {
           const double sj = (1.0 + complementary_variable_margin_rate) * std::max(-1 * g[j], complementary_variable_min);
           variable_.s[i * G + j] = sj;
@@ -510,11 +552,18 @@ public:
 
     checkVariable(); // :190
 
-    if(delta_variable_.T != T) // :193-197
+    if(kStepDims || delta_variable_.T != T) // :193-197
     {
       delta_variable_ = Variable(T, N, M, G);
     }
-    coeff_list_.resize(T + 1); // :211-218 (fixed dimensions: existing elements are preserved)
+    if constexpr(kStepDims) // :211-218: a step's records are sized anew, here cleared, so that k, K beyond m(i) are 0
+    {
+      coeff_list_.assign(T + 1, Coefficient());
+    }
+    else // fixed dimensions: existing elements are preserved
+    {
+      coeff_list_.resize(T + 1);
+    }
     for(int i = 0; i <= T; i++)
     {
       coeff_list_[i].terminal = (i == T);
@@ -561,15 +610,18 @@ public:
     {
       throw std::invalid_argument("[FMPC] nu_list length should be " + std::to_string(T) + ".");
     }
-    for(int i = 0; i < T * G; i++)
+    for(int i = 0; i < T; i++)
     {
-      if(variable_.s[i] < 0)
+      for(int j = 0; j < stepDims(i).g; j++)
       {
-        throw std::runtime_error("[FMPC] s_list[i] must be non-negative. i: " + std::to_string(i / G));
-      }
-      if(variable_.nu[i] < 0)
-      {
-        throw std::runtime_error("[FMPC] nu_list[i] must be non-negative. i: " + std::to_string(i / G));
+        if(variable_.s[i * G + j] < 0)
+        {
+          throw std::runtime_error("[FMPC] s_list[i] must be non-negative. i: " + std::to_string(i));
+        }
+        if(variable_.nu[i * G + j] < 0)
+        {
+          throw std::runtime_error("[FMPC] nu_list[i] must be non-negative. i: " + std::to_string(i));
+        }
       }
     }
   }
@@ -587,13 +639,14 @@ public:
       int total_ineq_dim = 0;
       for(int i = 0; i < T; i++)
       {
+        const int g = stepDims(i).g;
         double dot = 0;
-        for(int j = 0; j < G; j++)
+        for(int j = 0; j < g; j++)
         {
           dot += variable_.s[i * G + j] * variable_.nu[i * G + j];
         }
         s_nu_ave += dot;
-        total_ineq_dim += G;
+        total_ineq_dim += g;
       }
       s_nu_ave /= total_ineq_dim;
       const double sigma = 0.5;
@@ -609,6 +662,7 @@ public:
       for(int i = 0; i < T; i++)
       {
         Coefficient & c = coeff_list_[i];
+        const StepDims d = stepDims(i);
         const double t = current_t_ + i * dt;
         const double * x = &variable_.x[i * N];
         const double * next_x = &variable_.x[(i + 1) * N];
@@ -629,7 +683,7 @@ public:
         {
           c.x_bar[a] = f[a] - next_x[a]; // (2.23c)
         }
-        for(int a = 0; a < G; a++)
+        for(int a = 0; a < d.g; a++)
         {
           c.g_bar[a] = g[a] + s[a]; // (2.23d)
         }
@@ -640,20 +694,20 @@ public:
           {
             at += c.A[r + a * N] * next_lambda[r];
           }
-          for(int r = 0; r < G; r++)
+          for(int r = 0; r < d.g; r++)
           {
             ct += c.C[r + a * G] * nu[r];
           }
           c.Lx_bar[a] = ((-1 * lambda[a] + dt * c.Lx[a]) + at) + ct;
         }
-        for(int a = 0; a < M; a++) // (2.25c)
+        for(int a = 0; a < d.m; a++) // (2.25c)
         {
           double bt = 0, dtn = 0;
           for(int r = 0; r < N; r++)
           {
             bt += c.B[r + a * N] * next_lambda[r];
           }
-          for(int r = 0; r < G; r++)
+          for(int r = 0; r < d.g; r++)
           {
             dtn += c.D[r + a * G] * nu[r];
           }
@@ -713,12 +767,13 @@ public:
     for(int i = 0; i < T; i++)
     {
       const Coefficient & c = coeff_list_[i];
+      const StepDims d = stepDims(i);
       kkt_error += sq(c.x_bar, N);
-      kkt_error += sq(c.g_bar, G);
+      kkt_error += sq(c.g_bar, d.g);
       kkt_error += sq(c.Lx_bar, N);
-      kkt_error += sq(c.Lu_bar, M);
+      kkt_error += sq(c.Lu_bar, d.m);
       double comp = 0;
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < d.g; j++)
       {
         const double e = std::max(variable_.s[i * G + j] * variable_.nu[i * G + j] - barrier_eps, 0.0);
         comp += e * e;
@@ -748,12 +803,13 @@ public:
     for(int i = T - 1; i >= 0; i--)
     {
       Coefficient & c = coeff_list_[i];
+      const int m = stepDims(i).m, g = stepDims(i).g;
       const double * sv = &variable_.s[i * G];
       const double * nuv = &variable_.nu[i * G];
 
       // pre-process (:562-580)
       double nu_s[G > 0 ? G : 1], tilde_sub[G > 0 ? G : 1];
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < g; j++)
       {
         nu_s[j] = nuv[j] / sv[j];
         tilde_sub[j] = (nu_s[j] * c.g_bar[j] - nuv[j]) + barrier_eps_ * (1.0 / sv[j]);
@@ -765,19 +821,19 @@ public:
         for(int a = 0; a < N; a++)
         {
           double acc = 0;
-          for(int j = 0; j < G; j++)
+          for(int j = 0; j < g; j++)
           {
             acc += (c.C[j + a * G] * nu_s[j]) * c.C[j + b * G];
           }
           Qxx[a + b * N] = dt * c.Lxx[a + b * N] + acc; // (2.28c)
         }
       }
-      for(int b = 0; b < M; b++)
+      for(int b = 0; b < m; b++)
       {
-        for(int a = 0; a < M; a++)
+        for(int a = 0; a < m; a++)
         {
           double acc = 0;
-          for(int j = 0; j < G; j++)
+          for(int j = 0; j < g; j++)
           {
             acc += (c.D[j + a * G] * nu_s[j]) * c.D[j + b * G];
           }
@@ -786,7 +842,7 @@ public:
         for(int a = 0; a < N; a++)
         {
           double acc = 0;
-          for(int j = 0; j < G; j++)
+          for(int j = 0; j < g; j++)
           {
             acc += (c.C[j + a * G] * nu_s[j]) * c.D[j + b * G];
           }
@@ -796,16 +852,16 @@ public:
       for(int a = 0; a < N; a++)
       {
         double acc = 0;
-        for(int j = 0; j < G; j++)
+        for(int j = 0; j < g; j++)
         {
           acc += c.C[j + a * G] * tilde_sub[j];
         }
         Lx_t[a] = c.Lx_bar[a] + acc; // (2.28f)
       }
-      for(int a = 0; a < M; a++)
+      for(int a = 0; a < m; a++)
       {
         double acc = 0;
-        for(int j = 0; j < G; j++)
+        for(int j = 0; j < g; j++)
         {
           acc += c.D[j + a * G] * tilde_sub[j];
         }
@@ -824,7 +880,7 @@ public:
           }
           AtP[a + b * N] = acc;
         }
-        for(int a = 0; a < M; a++)
+        for(int a = 0; a < m; a++)
         {
           double acc = 0;
           for(int r = 0; r < N; r++)
@@ -834,7 +890,7 @@ public:
           BtP[a + b * M] = acc;
         }
       }
-      double F[N * N], H[N * M > 0 ? N * M : 1], Gm[M * M > 0 ? M * M : 1];
+      double F[N * N], H[N * M > 0 ? N * M : 1], Gm[M * M > 0 ? M * M : 1]; // Gm: m x m, leading dimension m (for Ldlt)
       for(int b = 0; b < N; b++)
       {
         for(int a = 0; a < N; a++)
@@ -847,7 +903,7 @@ public:
           F[a + b * N] = Qxx[a + b * N] + acc; // (2.35b)
         }
       }
-      for(int b = 0; b < M; b++)
+      for(int b = 0; b < m; b++)
       {
         for(int a = 0; a < N; a++)
         {
@@ -858,14 +914,14 @@ public:
           }
           H[a + b * N] = Qxu[a + b * N] + acc; // (2.35c)
         }
-        for(int a = 0; a < M; a++)
+        for(int a = 0; a < m; a++)
         {
           double acc = 0;
           for(int r = 0; r < N; r++)
           {
             acc += BtP[a + r * M] * c.B[r + b * N];
           }
-          Gm[a + b * M] = Quu[a + b * M] + acc; // (2.35d)
+          Gm[a + b * m] = Quu[a + b * M] + acc; // (2.35d)
         }
       }
 
@@ -880,10 +936,10 @@ public:
         }
         Px_s[a] = acc - s[a];
       }
-      double k[M > 0 ? M : 1], K[M * N > 0 ? M * N : 1];
-      if(M > 0)
+      double k[M > 0 ? M : 1], K[M * N > 0 ? M * N : 1]; // K: m x N, leading dimension m
+      if(m > 0)
       {
-        for(int a = 0; a < M; a++)
+        for(int a = 0; a < m; a++)
         {
           double acc = 0;
           for(int r = 0; r < N; r++)
@@ -894,13 +950,13 @@ public:
         }
         for(int b = 0; b < N; b++)
         {
-          for(int a = 0; a < M; a++)
+          for(int a = 0; a < m; a++)
           {
-            K[a + b * M] = H[b + a * N]; // H^T
+            K[a + b * m] = H[b + a * N]; // H^T
           }
         }
         Ldlt ldlt;
-        if(ldlt.compute(Gm, M))
+        if(ldlt.compute(Gm, m))
         {
           ldlt.solveInPlace(k, 1);
           ldlt.solveInPlace(K, N);
@@ -911,14 +967,14 @@ public:
           {
             return false;
           }
-          fullPivLuSolveInPlace(Gm, M, k, 1);
-          fullPivLuSolveInPlace(Gm, M, K, N);
+          fullPivLuSolveInPlace(Gm, m, k, 1);
+          fullPivLuSolveInPlace(Gm, m, K, N);
         }
-        for(int a = 0; a < M; a++)
+        for(int a = 0; a < m; a++)
         {
           k[a] = -1 * k[a]; // (2.35e)
         }
-        for(int a = 0; a < M * N; a++)
+        for(int a = 0; a < m * N; a++)
         {
           K[a] = -1 * K[a]; // (2.35e)
         }
@@ -933,7 +989,7 @@ public:
         {
           at += c.A[r + a * N] * (-1 * Px_s[r]); // A^T (s - P x_bar)
         }
-        for(int r = 0; r < M; r++)
+        for(int r = 0; r < m; r++)
         {
           hk += H[a + r * N] * k[r];
         }
@@ -941,14 +997,14 @@ public:
       }
       // K^T G K left to right: (K^T G) (n x m), then times K
       double KtG[N * M > 0 ? N * M : 1];
-      for(int b = 0; b < M; b++)
+      for(int b = 0; b < m; b++)
       {
         for(int a = 0; a < N; a++)
         {
           double acc = 0;
-          for(int r = 0; r < M; r++)
+          for(int r = 0; r < m; r++)
           {
-            acc += K[r + a * M] * Gm[r + b * M];
+            acc += K[r + a * m] * Gm[r + b * m];
           }
           KtG[a + b * N] = acc;
         }
@@ -958,9 +1014,9 @@ public:
         for(int a = 0; a < N; a++)
         {
           double acc = 0;
-          for(int r = 0; r < M; r++)
+          for(int r = 0; r < m; r++)
           {
-            acc += KtG[a + r * N] * K[r + b * M];
+            acc += KtG[a + r * N] * K[r + b * m];
           }
           P_new[a + b * N] = F[a + b * N] - acc; // (2.35a)
         }
@@ -974,8 +1030,14 @@ public:
       }
       std::copy(s_new, s_new + N, s);
 
-      std::copy(k, k + M, c.k); // :634-637
-      std::copy(K, K + M * N, c.K);
+      std::copy(k, k + m, c.k); // :634-637
+      for(int b = 0; b < N; b++)
+      {
+        for(int q = 0; q < m; q++)
+        {
+          c.K[q + b * M] = K[q + b * m];
+        }
+      }
       std::copy(s, s + N, c.s);
       std::copy(P, P + N * N, c.P);
     }
@@ -1017,8 +1079,9 @@ public:
       }
       if(i < T)
       {
+        const int m = stepDims(i).m;
         double * du = &d.u[i * M];
-        for(int a = 0; a < M; a++) // (2.36)
+        for(int a = 0; a < m; a++) // (2.36)
         {
           double acc = 0;
           for(int r = 0; r < N; r++)
@@ -1034,7 +1097,7 @@ public:
           {
             ax += c.A[a + r * N] * dx[r];
           }
-          for(int r = 0; r < M; r++)
+          for(int r = 0; r < m; r++)
           {
             bu += c.B[a + r * N] * du[r];
           }
@@ -1047,14 +1110,15 @@ public:
       const Coefficient & c = coeff_list_[i];
       const double * dx = &d.x[i * N];
       const double * du = &d.u[i * M];
-      for(int j = 0; j < G; j++)
+      const int m = stepDims(i).m, g = stepDims(i).g;
+      for(int j = 0; j < g; j++)
       {
         double cx = 0, du_ = 0;
         for(int r = 0; r < N; r++)
         {
           cx += c.C[j + r * G] * dx[r];
         }
-        for(int r = 0; r < M; r++)
+        for(int r = 0; r < m; r++)
         {
           du_ += c.D[j + r * G] * du[r];
         }
@@ -1081,15 +1145,18 @@ public:
     double alpha_nu_max = 1.0;
     {
       constexpr double margin_ratio = 0.995;
-      for(int i = 0; i < T * G; i++) // (19.9) in Nocedal & Wright
+      for(int i = 0; i < T; i++) // (19.9) in Nocedal & Wright
       {
-        if(d.s[i] < 0)
+        for(int j = i * G; j < i * G + stepDims(i).g; j++)
         {
-          alpha_s_max = std::min(alpha_s_max, -1 * margin_ratio * variable_.s[i] / d.s[i]);
-        }
-        if(d.nu[i] < 0)
-        {
-          alpha_nu_max = std::min(alpha_nu_max, -1 * margin_ratio * variable_.nu[i] / d.nu[i]);
+          if(d.s[j] < 0)
+          {
+            alpha_s_max = std::min(alpha_s_max, -1 * margin_ratio * variable_.s[j] / d.s[j]);
+          }
+          if(d.nu[j] < 0)
+          {
+            alpha_nu_max = std::min(alpha_nu_max, -1 * margin_ratio * variable_.nu[j] / d.nu[j]);
+          }
         }
       }
       if(!(alpha_s_max > 0.0 && alpha_s_max <= 1.0 && alpha_nu_max > 0.0 && alpha_nu_max <= 1.0))
@@ -1116,13 +1183,16 @@ public:
         {
           ls.x[i] = variable_.x[i] + alpha_s * d.x[i];
         }
-        for(size_t i = 0; i < ls.u.size(); i++)
+        for(int i = 0; i < T; i++)
         {
-          ls.u[i] = variable_.u[i] + alpha_s * d.u[i];
-        }
-        for(size_t i = 0; i < ls.s.size(); i++)
-        {
-          ls.s[i] = variable_.s[i] + alpha_s * d.s[i];
+          for(int j = i * M; j < i * M + stepDims(i).m; j++)
+          {
+            ls.u[j] = variable_.u[j] + alpha_s * d.u[j];
+          }
+          for(int j = i * G; j < i * G + stepDims(i).g; j++)
+          {
+            ls.s[j] = variable_.s[j] + alpha_s * d.s[j];
+          }
         }
         const double merit_func_new = calcMeritFunc(ls);
         if(merit_func_new < merit_func_ + armijo_scale * alpha_s * merit_deriv_)
@@ -1141,24 +1211,25 @@ public:
       variable_.x[i] += alpha_s * d.x[i];
       variable_.lambda[i] += alpha_nu * d.lambda[i];
     }
-    for(size_t i = 0; i < variable_.u.size(); i++)
-    {
-      variable_.u[i] += alpha_s * d.u[i];
-    }
     // `min_positive_value` of the reference is numeric_limits<double>::lowest() (:812), i.e. -DBL_MAX: the clamp below it
     // never changes a finite value.  Restated as written.
     constexpr double min_positive_value = std::numeric_limits<double>::lowest();
     for(int i = 0; i < T; i++)
     {
+      const int g = stepDims(i).g;
+      for(int j = i * M; j < i * M + stepDims(i).m; j++)
+      {
+        variable_.u[j] += alpha_s * d.u[j];
+      }
       bool s_neg = false, nu_neg = false;
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < g; j++)
       {
         variable_.s[i * G + j] += alpha_s * d.s[i * G + j];
         variable_.nu[i * G + j] += alpha_nu * d.nu[i * G + j];
         s_neg = s_neg || variable_.s[i * G + j] < 0;
         nu_neg = nu_neg || variable_.nu[i * G + j] < 0;
       }
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < g; j++)
       {
         if(s_neg)
         {
@@ -1212,7 +1283,7 @@ public:
         cf[a] = current_x_[a] - variable_.x[a];
       }
       merit_func_const += l1(cf, N);
-      merit_deriv_const += l1NormDirectionalDeriv(cf, neg_I, &d.x[0], N, N);
+      merit_deriv_const += l1NormDirectionalDeriv(cf, neg_I, N, &d.x[0], N, N);
     }
     for(int i = 0; i < T; i++)
     {
@@ -1226,12 +1297,13 @@ public:
       const double * ds = &d.s[i * G];
       const double * dnx = &d.x[(i + 1) * N];
       const Coefficient & c = coeff_list_[i];
+      const int m = stepDims(i).m, g = stepDims(i).g;
 
       merit_func_obj += problem_.runningCost(t, x, u) * dt;
-      merit_deriv_obj += (dot(c.Lx, dx, N) + dot(c.Lu, du, M)) * dt;
+      merit_deriv_obj += (dot(c.Lx, dx, N) + dot(c.Lu, du, m)) * dt;
 
       double logsum = 0, invdot = 0;
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < g; j++)
       {
         logsum += std::log(s[j]);
         invdot += (1.0 / s[j]) * ds[j];
@@ -1247,21 +1319,21 @@ public:
           cf[a] = f[a] - next_x[a];
         }
         merit_func_const += l1(cf, N);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, c.A, dx, N, N);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, c.B, du, N, M);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, neg_I, dnx, N, N);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, c.A, N, dx, N, N);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, c.B, N, du, N, m);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, neg_I, N, dnx, N, N);
       }
       {
-        double g[G > 0 ? G : 1], cf[G > 0 ? G : 1];
-        problem_.ineqConst(t, x, u, g);
-        for(int a = 0; a < G; a++)
+        double gv[G > 0 ? G : 1], cf[G > 0 ? G : 1];
+        problem_.ineqConst(t, x, u, gv);
+        for(int a = 0; a < g; a++)
         {
-          cf[a] = g[a] + s[a];
+          cf[a] = gv[a] + s[a];
         }
-        merit_func_const += l1(cf, G);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, c.C, dx, G, N);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, c.D, du, G, M);
-        merit_deriv_const += l1NormDirectionalDeriv(cf, I_g, ds, G, G);
+        merit_func_const += l1(cf, g);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, c.C, G, dx, g, N);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, c.D, G, du, g, m);
+        merit_deriv_const += l1NormDirectionalDeriv(cf, I_g, G, ds, g, g);
       }
     }
     {
@@ -1278,9 +1350,12 @@ public:
       {
         merit_const_scale_ = std::max(merit_const_scale_, std::abs(v));
       }
-      for(double v : variable_.nu)
+      for(int i = 0; i < T; i++)
       {
-        merit_const_scale_ = std::max(merit_const_scale_, std::abs(v));
+        for(int j = i * G; j < i * G + stepDims(i).g; j++)
+        {
+          merit_const_scale_ = std::max(merit_const_scale_, std::abs(variable_.nu[j]));
+        }
       }
     }
     else // (18.33)
@@ -1308,14 +1383,15 @@ public:
       const double * x = &v.x[i * N];
       const double * u = &v.u[i * M];
       const double * s = &v.s[i * G];
+      const int g = stepDims(i).g;
       merit_func_obj += problem_.runningCost(t, x, u) * dt;
       double logsum = 0;
-      for(int j = 0; j < G; j++)
+      for(int j = 0; j < g; j++)
       {
         logsum += std::log(s[j]);
       }
       merit_func_obj += -1 * barrier_eps_ * logsum;
-      double f[N], g[G > 0 ? G : 1];
+      double f[N], gv[G > 0 ? G : 1];
       problem_.stateEq(t, x, u, f);
       double c1 = 0;
       for(int a = 0; a < N; a++)
@@ -1323,11 +1399,11 @@ public:
         c1 += std::abs(f[a] - v.x[(i + 1) * N + a]);
       }
       merit_func_const += c1;
-      problem_.ineqConst(t, x, u, g);
+      problem_.ineqConst(t, x, u, gv);
       double c2 = 0;
-      for(int a = 0; a < G; a++)
+      for(int a = 0; a < g; a++)
       {
-        c2 += std::abs(g[a] + s[a]);
+        c2 += std::abs(gv[a] + s[a]);
       }
       merit_func_const += c2;
     }
@@ -1356,6 +1432,7 @@ protected:
   Variable variable_;
   Variable delta_variable_;
   std::vector<Coefficient> coeff_list_;
+  std::vector<StepDims> step_dims_; // of the last solve; used only where kStepDims
   std::vector<TraceRow> trace_data_list_;
   double barrier_eps_ = 1e-4; // FmpcSolver.h:414
   double merit_const_scale_ = 0.0;

@@ -1,7 +1,8 @@
 """FMPC problems with time-varying input / inequality dimensions, what can be checked without a GPU: the registration of
-fmpc_vertical and its dimensions, its parameter image, the host-side inputDim(t) / ineqDim(t), and the CPU checker
-(tests/cpp/fmpc_dynamic_checker.cpp) — anchored to the FMPC oracle on the three fixed-dimension models, and converging on
-fmpc_vertical with its forces inside their bounds."""
+fmpc_vertical and its dimensions, its parameter image, the host-side inputDim(t) / ineqDim(t), and the CPU FMPC oracle on
+fmpc_vertical (`checker` is oracle/fmpc.py in the library's layouts, tests/fmpc_dynamic_checker.py) — reproducing bit for bit the
+vectors recorded in tests/golden/fmpc_vertical_golden.npz, and converging with its forces inside their bounds."""
+import importlib.util
 import os
 import re
 from types import SimpleNamespace
@@ -19,8 +20,8 @@ SWITCHES = (2.0, 3.0, 4.5, 5.0)
 
 
 @pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return DC.build(tmp_path_factory.mktemp("fmpc_dynamic_checker"))
+def checker():
+    return DC
 
 
 def test_vertical_is_registered_with_capacities_and_dynamic_flags():
@@ -87,6 +88,8 @@ def _rel_close(a, b, rtol=1e-10, atol=1e-13):
 @pytest.mark.parametrize("opts", [{}, {"enable_line_search": 1}, {"init_complementary_variable": 1}, {"update_barrier_eps": 0},
                                   {"enable_line_search": 1, "merit_const_scale_from_lagrange_multipliers": 1}])
 def test_checker_equals_the_oracle_on_fixed_dimensions(checker, model, opts):
+    """The threaded batch entry point with every output, in the library's layouts (`checker`), against the single solve O.solve:
+    both are the one oracle now, so this pins the batch path's strides, the packing of its outputs and the adapter's layouts."""
     n, m, g, _ = O.model_info(model)
     B, T = 12, 25
     rng = np.random.default_rng(7 + len(opts))
@@ -112,6 +115,47 @@ def test_checker_equals_the_oracle_on_fixed_dimensions(checker, model, opts):
         assert _rel_close(r.barrier_eps[b], o.barrier_eps)
         compared += 1
     assert compared >= B // 2, compared
+
+
+def _golden():
+    here = os.path.join(ROOT, "tests", "golden")
+    spec = importlib.util.spec_from_file_location("make_fmpc_vertical_golden", os.path.join(here, "make_fmpc_vertical_golden.py"))
+    make = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make)
+    return make, np.load(os.path.join(here, "fmpc_vertical_golden.npz"))
+
+
+MAKE, GOLDEN = _golden()
+
+
+@pytest.mark.parametrize("name", MAKE.SOLVES + ("loop",))
+def test_oracle_reproduces_the_vertical_golden_bit_for_bit(name):
+    """Every stored array of every instance, diverging or not: the file holds what the per-step-dimension checker that preceded
+    the oracle's dims(t) computed, from the inputs stored next to it."""
+    got = MAKE.run_loop(GOLDEN) if name == "loop" else MAKE.run_solve(name, GOLDEN)
+    stored = {k.split("/", 1)[1] for k in GOLDEN.files if k.startswith(name + "/")}
+    assert stored == set(got) and stored
+    for k, a in got.items():
+        want = GOLDEN[f"{name}/{k}"]
+        assert a.dtype == want.dtype and np.array_equal(a, want, equal_nan=True), (name, k)
+
+
+def test_vertical_golden_covers_its_cases():
+    """The recorded horizons hold every switch of the input dimension, a horizon without inequality rows that succeeds at its
+    second iteration, poison beyond every step's dimensions, and its inputs are what the generator draws."""
+    inputs = MAKE.make_inputs()
+    for k, a in inputs.items():
+        assert np.array_equal(a, GOLDEN[k]), k
+    t0 = GOLDEN["t0"]
+    md = np.array([[DC.dims_at("fmpc_vertical", t + i * 0.01)[0] for i in range(MAKE.T)] for t in t0])
+    steps = {(a, b) for row in md for a, b in zip(row[:-1], row[1:]) if a != b}
+    assert steps == {(1, 2), (2, 1), (1, 0), (0, 1)}
+    assert (md == 2).all(axis=1).any() and (md == 0).all(axis=1).sum() == 1
+    none = int(np.argmax((md == 0).all(axis=1)))
+    assert GOLDEN["default/status"][none] == 1 and GOLDEN["default/iters"][none] == 2
+    assert (GOLDEN["in_u"][md < 2][:, 1] == MAKE.POISON).all() and (GOLDEN["default/u"][md < 2][:, 1] == MAKE.POISON).all()
+    assert (GOLDEN["default/du"][md < 2][:, 1] == 0).all()
+    assert np.isin(GOLDEN["loop/status_log"], (1, 5)).all()
 
 
 def test_checker_converges_on_vertical_with_forces_in_bounds(checker):

@@ -1,6 +1,7 @@
 """FMPC with time-varying input / inequality dimensions on the MI355X (fmpc_vertical: 1, 2, 1, 0, 1 contacts), against the CPU
-checker tests/cpp/fmpc_dynamic_checker.cpp (a restatement of FmpcSolver::solve with per-step dimensions, pinned to the FMPC oracle
-on the fixed-dimension models by tests/test_fmpc_dynamic_host_cpu.py).
+FMPC oracle (oracle/fmpc_oracle.hpp, which sizes every step by the model's dims(t); `checker` below is that oracle in the
+library's layouts, tests/fmpc_dynamic_checker.py).  The oracle is pinned by the reference's assertions on the fixed-dimension models
+(tests/test_fmpc_oracle_pins.py) and bit for bit by recorded vectors on fmpc_vertical (tests/test_fmpc_dynamic_host_cpu.py).
 
 Bar: as tests/test_gpu_fmpc.py — equal statuses and iteration counts, floating-point results within 1e-8 relative / 1e-10
 absolute (the device contracts a * b + c into FMAs, the checker is built with -ffp-contract=off), on the instances whose iteration
@@ -21,8 +22,8 @@ POISON = -1234.5  # a value no solve may read or write beyond a step's dimension
 
 
 @pytest.fixture(scope="module")
-def checker(tmp_path_factory):
-    return DC.build(tmp_path_factory.mktemp("fmpc_dynamic_checker"))
+def checker():
+    return DC
 
 
 def make_case(B, T, seed, t_hi=6.0, poison=True):
