@@ -8,3 +8,4 @@ from .ddp import (ComputationDuration, Configuration, ControlData, DDPSolverBatc
 from .models import (DDPProblemBipedal, DDPProblemCartPole, DDPProblemCartPoleF32, DDPProblemCentroidalMotion,  # noqa: F401
                      DDPProblemManipulator, DDPProblemManipulatorF32, DDPProblemQuadrotor, DDPProblemVerticalMotion, make_problem)
 from .cgmres import CgmresProblem, CgmresProblemCartPole, CgmresProblemSemiactiveDamper, CgmresSolverBatch  # noqa: F401
+from .boxqp import BoxQPBatch  # noqa: F401
