@@ -524,20 +524,27 @@ def test_max_iter_zero_returns_uninitialized():
         assert np.array_equal(a, c)
 
 
-def test_fused_riccati_kernel_returns_the_quad_kernels_bits(monkeypatch):
+# the shipped shape, then the smallest ones at which the chunk protocol of either kernel can go wrong: (17, 3) one partial backward
+# chunk, the second producer wave idle, one partial forward chunk, a second workgroup with one live lane; (1, 5) N = 2, two backward
+# chunks, fifteen mirrored lanes; (33, 12) an odd number of backward chunks, two forward chunks of which the last is partial
+@pytest.mark.parametrize("model,B,T,max_iter", [("fmpc_cartpole", 200, 61, 4), ("fmpc_cartpole", 17, 3, 2), ("fmpc_oscillator", 1, 5, 2),
+                                                ("fmpc_oscillator", 33, 12, 2)])
+def test_fused_riccati_kernel_returns_the_quad_kernels_bits(model, B, T, max_iter, monkeypatch):
     """fmpc_riccati_fused_kernel computes the coefficient records in its producer waves (fmpc::coefficients, the body of the coefficient
     kernel with another sink) and runs the quad kernel's recursion on them: the same statements on the same values — every output of a
-    solve is bit-identical to the unfused path's (coefficient kernel + records through HBM + fmpc_riccati_quad_kernel)."""
+    solve is bit-identical to the unfused path's (coefficient kernel + records through HBM + fmpc_riccati_quad_kernel).  No convergence
+    is needed for that."""
     res = {}
     for riccati in ("quad", "fused"):
         monkeypatch.setenv("NMPC_HIP_FMPC_RICCATI", riccati)
-        prob = F.FmpcProblemCartPole()
-        var, x0, t0 = make_case("fmpc_cartpole", 200, 61, seed=7)
-        s = F.FmpcSolverBatch(prob, 200, 61)
-        s.config().max_iter = 4
+        prob = MODELS[model]()
+        var, x0, t0 = make_case(model, B, T, seed=7)
+        s = F.FmpcSolverBatch(prob, B, T)
+        s.config().max_iter = max_iter
         s.solve(t0, x0, var)
         assert ("fmpc_riccati_%s_kernel" % riccati) in s.kernelNames()
         cl = s.coeffList()
-        res[riccati] = [a.copy() for a in s.variable().arrays()] + [s.traceDataList().copy(), s.iters().copy(), cl["K"].copy(), cl["P"].copy()]
+        res[riccati] = [a.copy() for a in s.variable().arrays()] + [s.traceDataList().copy(), s.iters().copy(), cl["K"].copy(), cl["P"].copy(),
+                                                                    s.status().copy()]
     for a, b in zip(res["quad"], res["fused"]):
         assert np.array_equal(a, b, equal_nan=True)
