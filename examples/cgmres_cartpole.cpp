@@ -6,12 +6,16 @@
 //
 //   g++ -std=c++17 -O2 -Iinclude -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ examples/cgmres_cartpole.cpp -Lnmpc_amd/lib
 //       -lnmpc_hip_ddp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$PWD/nmpc_amd/lib -o cgmres_cartpole
-//   ./cgmres_cartpole [batch=256] [seconds=20]
+//   ./cgmres_cartpole [batch=256] [seconds=20] [--kernel lane|wave]
+//
+// --kernel wave ticks every controller on a wavefront of its own with the horizon in LDS (the low-latency kernel for fleets of up
+// to a few thousand; the same inputs bit for bit); the default is the lane kernel (one lane per controller).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -33,8 +37,21 @@ using Solver = nmpc_amd::CgmresSolverBatch<Problem>;
 
 int main(int argc, char ** argv)
 {
-  const int B = argc > 1 ? std::atoi(argv[1]) : 256;
-  const double seconds = argc > 2 ? std::atof(argv[2]) : 20.0;
+  const char * kernel = "lane";
+  std::vector<const char *> pos;
+  for(int i = 1; i < argc; i++)
+  {
+    if(std::strcmp(argv[i], "--kernel") == 0 && i + 1 < argc)
+    {
+      kernel = argv[++i];
+    }
+    else
+    {
+      pos.push_back(argv[i]);
+    }
+  }
+  const int B = pos.size() > 0 ? std::atoi(pos[0]) : 256;
+  const double seconds = pos.size() > 1 ? std::atof(pos[1]) : 20.0;
   constexpr int NX = Problem::dim_x_, NUC = Problem::dim_uc_;
   auto problem = std::make_shared<Problem>();
   Solver solver(problem, B, 25, NMPC_HIP_CGMRES_ODE_EULER);
@@ -42,6 +59,7 @@ int main(int argc, char ** argv)
   {
     solver.x_initial_[b][1] += 0.02 * (b % 16) / 16.0 - 0.01; // a spread of pole angles around hanging down
   }
+  solver.setKernel(kernel); // throws std::invalid_argument for an unknown name or a shape past the wave kernel's LDS budget
   solver.setup();
   std::vector<double> t(B), x(B * NX), next_x(B * NX), u(B * NUC);
   for(int b = 0; b < B; b++)
@@ -101,7 +119,8 @@ int main(int argc, char ** argv)
     upright += std::sqrt(n2) < 0.1;
     non_finite += !std::isfinite(n2);
   }
-  std::printf("%d cart-poles, %d ticks of %g s: %d upright (|x| < 0.1), %d non-finite\n", B, ticks, dt, upright, non_finite);
+  std::printf("%d cart-poles, %d ticks of %g s on %s: %d upright (|x| < 0.1), %d non-finite\n", B, ticks, dt, solver.kernelName().c_str(),
+              upright, non_finite);
   (void)hipFree(d_t);
   (void)hipFree(d_x);
   (void)hipFree(d_nx);

@@ -91,6 +91,27 @@ public:
     check(nmpc_hip_cgmres_control_input_device(h_, d_t, d_x, d_next_x, d_u, stream));
   }
 
+  /** "lane" (default) or "wave" (one wavefront per instance, the tick in LDS; <nmpc_hip_cgmres.h>): the kernel family of run and
+      calcControlInput.  Same bits either way.  Throws std::invalid_argument when the problem type has no wave kernels or the shape
+      (horizon_divide_num_, k_max_) exceeds their LDS budget. */
+  void setKernel(const char * kernel)
+  {
+    if(kernel && std::string(kernel) == "wave") // the handle has to know k_max_ to judge the shape; "lane" takes every config
+    {
+      pushConfig();
+    }
+    check(nmpc_hip_cgmres_set_kernel(h_, kernel));
+    pushConfig();
+  }
+
+  /** The kernel symbol run() launches next: "cgmres_run_kernel" or "cgmres_wave_run_kernel". */
+  std::string kernelName() const
+  {
+    const char * name = nullptr;
+    check(nmpc_hip_cgmres_kernel_name(h_, &name));
+    return name;
+  }
+
   void synchronize()
   {
     check(nmpc_hip_cgmres_synchronize(h_));

@@ -111,6 +111,21 @@ extern "C"
   int nmpc_hip_cgmres_create(const char * model, int horizon_divide_num, int batch, int device, nmpc_hip_cgmres_handle * out);
   int nmpc_hip_cgmres_destroy(nmpc_hip_cgmres_handle h);
 
+  /** Kernel family of run / control_input / control_input_device: "lane" (the default: one lane per instance, every list in HBM; a
+      throughput kernel for very large batches) or "wave" (one wavefront per instance, the whole tick in LDS; the low-latency kernel
+      for 1 .. a few thousand instances that have to tick inside dt).  Both read and write the same handle state and give the same
+      bits, so the kernel may be changed between calls.  "wave" is refused with NMPC_HIP_ERR_INVALID_ARGUMENT (the message names the
+      bytes) when the problem type has no wave registration (NMPC_AMD_REGISTER_CGMRES_WAVE_PROBLEM,
+      <nmpc_amd/hip/cgmres_wave_kernels.hpp>) or the shape needs more than 64 KiB of LDS; while "wave" is set, a set_config that raises
+      k_max past that budget is refused the same way and leaves the config as it was.  A NULL or unknown name is an invalid argument. */
+  int nmpc_hip_cgmres_set_kernel(nmpc_hip_cgmres_handle h, const char * kernel);
+  /** The kernel symbol run launches next, without template arguments: "cgmres_run_kernel" or "cgmres_wave_run_kernel". */
+  int nmpc_hip_cgmres_kernel_name(nmpc_hip_cgmres_handle h, const char ** name);
+  /** LDS bytes of one workgroup of the wave kernels for a registered problem type: with n = N * dim_uc, K = k_max,
+      8 * (4 n + 3 ((2 N + 1) dim_x + N) + (K + 3) n + K * K + 3 K + 1)  (layout: <nmpc_amd/hip/cgmres_wave_kernels.hpp>).  Needs no
+      device. */
+  int nmpc_hip_cgmres_wave_lds_bytes(const char * model, int horizon_divide_num, int k_max, size_t * bytes);
+
   int nmpc_hip_cgmres_set_config(nmpc_hip_cgmres_handle h, const nmpc_hip_cgmres_config * cfg);
   int nmpc_hip_cgmres_get_config(nmpc_hip_cgmres_handle h, nmpc_hip_cgmres_config * cfg);
 

@@ -54,7 +54,8 @@ EXPORTS = (
     "nmpc_hip_cgmres_get_config", "nmpc_hip_cgmres_set_problem", "nmpc_hip_cgmres_set_initial", "nmpc_hip_cgmres_setup",
     "nmpc_hip_cgmres_run", "nmpc_hip_cgmres_control_input", "nmpc_hip_cgmres_control_input_device", "nmpc_hip_cgmres_synchronize",
     "nmpc_hip_cgmres_get", "nmpc_hip_cgmres_field_bytes", "nmpc_hip_cgmres_dense_gmres", "nmpc_hip_cgmres_model_eval",
-    "nmpc_hip_cgmres_last_ms", "nmpc_hip_cgmres_last_error",
+    "nmpc_hip_cgmres_last_ms", "nmpc_hip_cgmres_last_error", "nmpc_hip_cgmres_set_kernel", "nmpc_hip_cgmres_kernel_name",
+    "nmpc_hip_cgmres_wave_lds_bytes",
 )
 
 _declared = False
@@ -88,6 +89,9 @@ def load():
     L.nmpc_hip_cgmres_dense_gmres.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, dp, C.c_int, C.c_int, C.c_double, ip, ip]
     L.nmpc_hip_cgmres_model_eval.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
     L.nmpc_hip_cgmres_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.nmpc_hip_cgmres_set_kernel.argtypes = [vp, C.c_char_p]
+    L.nmpc_hip_cgmres_kernel_name.argtypes = [vp, C.POINTER(C.c_char_p)]
+    L.nmpc_hip_cgmres_wave_lds_bytes.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(sz)]
     L.nmpc_hip_cgmres_last_error.argtypes = []
     L.nmpc_hip_cgmres_last_error.restype = C.c_char_p
     for name in EXPORTS:
@@ -139,6 +143,14 @@ def model_info(model: str):
     x0, u0 = np.zeros(nx.value), np.zeros(nu.value + nc.value)
     check(L.nmpc_hip_cgmres_model_info(model.encode(), None, None, None, None, _dp(x0), _dp(u0)))
     return nx.value, nu.value, nc.value, pb.value, x0, u0
+
+
+def wave_lds_bytes(model: str, horizon_divide_num: int, k_max: int) -> int:
+    """LDS bytes one workgroup of the wave kernels needs for a registered problem type (no device needed); a handle accepts
+    setKernel("wave") up to 65536."""
+    n = C.c_size_t()
+    check(load().nmpc_hip_cgmres_wave_lds_bytes(model.encode(), horizon_divide_num, k_max, C.byref(n)))
+    return n.value
 
 
 class CgmresProblem:
@@ -260,6 +272,21 @@ class CgmresSolverBatch:
 
     def _push(self):
         check(self._L.nmpc_hip_cgmres_set_config(self._h, C.byref(self._cfg)))
+
+    def setKernel(self, kernel: str) -> None:
+        """"lane" (default: one lane per instance) or "wave" (one wavefront per instance, the tick in LDS): the kernel family of run()
+        and calcControlInput*().  Same results bit for bit; may be changed between calls.  ValueError when the problem type has no
+        wave kernels or the shape (horizon_divide_num_, k_max_) exceeds their LDS budget."""
+        if kernel == "wave":  # the handle has to know k_max_ to judge the shape; "lane" takes every config, so it is set first
+            self._push()
+        check(self._L.nmpc_hip_cgmres_set_kernel(self._h, kernel.encode()))
+        self._push()
+
+    def kernelName(self) -> str:
+        """The kernel symbol run() launches next: "cgmres_run_kernel" or "cgmres_wave_run_kernel"."""
+        p = C.c_char_p()
+        check(self._L.nmpc_hip_cgmres_kernel_name(self._h, C.byref(p)))
+        return p.value.decode()
 
     def setProblem(self, problem) -> None:
         if isinstance(problem, (list, tuple)):

@@ -11,10 +11,12 @@
 
 #define NMPC_AMD_CGMRES_COMMON_KERNELS // cgmres_gmres_dense_kernel lives in this translation unit
 #include <nmpc_amd/hip/cgmres_kernels.hpp>
+#include <nmpc_amd/hip/cgmres_wave_kernels.hpp> // CgmresWaveOps and waveLdsBytes; the wave kernels live in cgmres_wave_models.hip
 
 namespace cg = nmpc_amd::hip::cgmres;
 using cg::CgmresBuffers;
 using cg::CgmresOps;
+using cg::CgmresWaveOps;
 
 namespace
 {
@@ -49,6 +51,24 @@ const CgmresOps * findModel(const char * name)
     return nullptr;
   }
   for(const CgmresOps * m : registry())
+  {
+    if(std::strcmp(m->name, name) == 0)
+    {
+      return m;
+    }
+  }
+  return nullptr;
+}
+
+std::vector<const CgmresWaveOps *> & waveRegistry()
+{
+  static std::vector<const CgmresWaveOps *> r;
+  return r;
+}
+
+const CgmresWaveOps * findWaveModel(const char * name)
+{
+  for(const CgmresWaveOps * m : waveRegistry())
   {
     if(std::strcmp(m->name, name) == 0)
     {
@@ -144,6 +164,8 @@ struct nmpc_hip_cgmres_solver
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float last_ms = 0;
   bool set_up = false;
+  const CgmresWaveOps * wave = nullptr; // non-NULL: run / control_input launch the wave kernels
+  size_t wave_lds = 0; // their LDS bytes for (N, cfg.k_max)
 };
 
 namespace
@@ -182,6 +204,33 @@ int validConfig(const nmpc_hip_cgmres_config & c, int horizon_divide_num)
     return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[C/GMRES] dump_step / ticks_per_launch / ODE solver out of range");
   }
   return NMPC_HIP_OK;
+}
+
+/** NMPC_HIP_OK when the wave kernels of problem type m fit the LDS budget at (N, k_max); the refusal names the bytes. */
+int waveFits(const CgmresOps * m, int N, int k_max, size_t * bytes)
+{
+  *bytes = cg::waveLdsBytes(N, m->nx, m->nuc, k_max);
+  if(*bytes > cg::kWaveMaxLdsBytes)
+  {
+    return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, std::string("[C/GMRES] the wave kernel of ") + m->name + " needs " + std::to_string(*bytes)
+                                                   + " bytes of LDS at horizon_divide_num = " + std::to_string(N) + ", k_max = "
+                                                   + std::to_string(k_max) + "; the budget is " + std::to_string(cg::kWaveMaxLdsBytes)
+                                                   + " (use the lane kernel)");
+  }
+  return NMPC_HIP_OK;
+}
+
+hipError_t launchRun(nmpc_hip_cgmres_solver * h, int i0, int n_ticks, double t0)
+{
+  return h->wave ? h->wave->launch_run(h->bf, i0, n_ticks, t0, h->wave_lds, h->stream)
+                 : h->ops->launch_run(h->bf, i0, n_ticks, t0, h->stream);
+}
+
+hipError_t launchControlInput(nmpc_hip_cgmres_solver * h, const double * t, const double * x, const double * next_x, double * u,
+                              hipStream_t s)
+{
+  return h->wave ? h->wave->launch_control_input(h->bf, t, x, next_x, u, h->wave_lds, s)
+                 : h->ops->launch_control_input(h->bf, t, x, next_x, u, s);
 }
 
 void applyConfig(nmpc_hip_cgmres_solver * h)
@@ -239,6 +288,76 @@ extern "C"
       return NMPC_HIP_ERR_INVALID_ARGUMENT;
     }
     registry().push_back(ops);
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_cgmres_register_wave_model(const CgmresWaveOps * ops)
+  {
+    if(!ops || !ops->name || findWaveModel(ops->name))
+    {
+      return NMPC_HIP_ERR_INVALID_ARGUMENT;
+    }
+    waveRegistry().push_back(ops);
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_cgmres_wave_lds_bytes(const char * model, int horizon_divide_num, int k_max, size_t * bytes)
+  {
+    const CgmresOps * m = findModel(model);
+    if(!m)
+    {
+      return unknownModel(model);
+    }
+    if(!bytes || horizon_divide_num < 1 || horizon_divide_num > 100000 || k_max < 1 || k_max > cg::kMaxKmax)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[C/GMRES] wave_lds_bytes: horizon_divide_num >= 1, k_max in 1 .. 16, bytes non-NULL");
+    }
+    *bytes = cg::waveLdsBytes(horizon_divide_num, m->nx, m->nuc, k_max);
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_cgmres_set_kernel(nmpc_hip_cgmres_handle h, const char * kernel)
+  {
+    if(!h || !kernel)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    }
+    if(std::strcmp(kernel, "lane") == 0)
+    {
+      h->wave = nullptr;
+      h->wave_lds = 0;
+      return NMPC_HIP_OK;
+    }
+    if(std::strcmp(kernel, "wave") != 0)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, std::string("[C/GMRES] unknown kernel \"") + kernel + "\": \"lane\" or \"wave\"");
+    }
+    const CgmresWaveOps * w = findWaveModel(h->ops->name);
+    if(!w || w->nx != h->ops->nx || w->nuc != h->ops->nuc)
+    {
+      size_t bytes = cg::waveLdsBytes(h->bf.N, h->ops->nx, h->ops->nuc, h->cfg.k_max);
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, std::string("[C/GMRES] problem type ") + h->ops->name
+                                                     + " has no wave kernels (NMPC_AMD_REGISTER_CGMRES_WAVE_PROBLEM); they would need "
+                                                     + std::to_string(bytes) + " bytes of LDS");
+    }
+    size_t bytes = 0;
+    const int rc = waveFits(h->ops, h->bf.N, h->cfg.k_max, &bytes);
+    if(rc != NMPC_HIP_OK)
+    {
+      return rc;
+    }
+    h->wave = w;
+    h->wave_lds = bytes;
+    return NMPC_HIP_OK;
+  }
+
+  int nmpc_hip_cgmres_kernel_name(nmpc_hip_cgmres_handle h, const char ** name)
+  {
+    if(!h || !name)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
+    }
+    *name = h->wave ? "cgmres_wave_run_kernel" : "cgmres_run_kernel";
     return NMPC_HIP_OK;
   }
 
@@ -479,6 +598,17 @@ extern "C"
     {
       return rc;
     }
+    if(h->wave)
+    {
+      // a k_max past the wave kernel's LDS budget: refused, the config stays as it was
+      size_t bytes = 0;
+      const int rw = waveFits(h->ops, h->bf.N, cfg->k_max, &bytes);
+      if(rw != NMPC_HIP_OK)
+      {
+        return rw;
+      }
+      h->wave_lds = bytes;
+    }
     h->cfg = *cfg;
     applyConfig(h);
     return NMPC_HIP_OK;
@@ -618,7 +748,7 @@ extern "C"
     }
     for(int i0 = 0; i0 < n_ticks; i0 += chunk)
     {
-      CG_TRY(h->ops->launch_run(b, i0, std::min(chunk, n_ticks - i0), ts[i0], h->stream));
+      CG_TRY(launchRun(h, i0, std::min(chunk, n_ticks - i0), ts[i0]));
     }
     return finishTimed(h);
   }
@@ -636,7 +766,7 @@ extern "C"
     }
     CG_TRY(hipSetDevice(h->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    CG_TRY(h->ops->launch_control_input(h->bf, d_t, d_x, d_next_x, d_u, s));
+    CG_TRY(launchControlInput(h, d_t, d_x, d_next_x, d_u, s));
     return NMPC_HIP_OK;
   }
 
@@ -660,7 +790,7 @@ extern "C"
     CG_TRY(hipMemcpyAsync(dt, t, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
     CG_TRY(hipMemcpyAsync(dx, x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
     CG_TRY(hipMemcpyAsync(dnx, next_x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CG_TRY(h->ops->launch_control_input(h->bf, dt, dx, dnx, du, h->stream));
+    CG_TRY(launchControlInput(h, dt, dx, dnx, du, h->stream));
     CG_TRY(hipMemcpyAsync(u, du, B * NUC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return finishTimed(h);
   }
