@@ -270,10 +270,26 @@ public:
   /** \brief A QUEUE of instances through the solver's batch_size slots (nmpc_hip_ddp_solve_stream): any number of problems, each
       solved to ITS convergence as DDPSolver::solve does (DDPSolver.hpp:26-141, 115-123); the slot of an instance that has finished
       takes the next one of the queue after at most `span` (0: 8) further iterations.  Every instance returns the bits of its lone
-      solve on the same kernel family.  State dimension <= 4, one input, fp64; shared problem object and constant limits. */
+      solve on the same kernel family.  State dimension <= 4, one input, fp64; every instance solves the solver's problem under the
+      solver's (constant) limits. */
   StreamResult solveStream(const std::vector<double> & current_t,
                            const std::vector<StateDimVector> & current_x,
                            const std::vector<std::vector<InputDimVector>> & initial_u_list,
+                           int span = 0)
+  {
+    return solveStream(current_t, current_x, initial_u_list, std::vector<Problem>(), std::vector<std::array<InputDimVector, 2>>(), span);
+  }
+
+  /** \brief A heterogeneous queue (nmpc_hip_ddp_solve_stream_ex): instance q solves problems[q] within limits[q] = {lower, upper}
+      (constant in time) — one DDPSolver per problem, each built with its own problem object and its own setInputLimitsFunc, run
+      through batch_size slots.  Either vector may be empty (the solver's shared problem / limits); with both empty this is the
+      overload above.  dt() and inputDim(t) of every problem must be those of the shared one.  Every instance returns the bits of its
+      lone solve (solve() with setProblemBatch / setInputLimitsBatch); afterwards the solver has its shared problem and limits again. */
+  StreamResult solveStream(const std::vector<double> & current_t,
+                           const std::vector<StateDimVector> & current_x,
+                           const std::vector<std::vector<InputDimVector>> & initial_u_list,
+                           const std::vector<Problem> & problems,
+                           const std::vector<std::array<InputDimVector, 2>> & limits,
                            int span = 0)
   {
     const int T = config_.horizon_steps;
@@ -307,7 +323,35 @@ public:
         }
       }
     }
-    check(nmpc_hip_ddp_solve_stream(handle_, static_cast<int>(N), current_t.data(), x0.data(), u0.data(), span));
+    if((!problems.empty() && problems.size() != N) || (!limits.empty() && limits.size() != N))
+    {
+      throw std::invalid_argument("problems / limits should have one entry per instance of the queue (" + std::to_string(N) + ") or none.");
+    }
+    if(problems.empty() && limits.empty())
+    {
+      check(nmpc_hip_ddp_solve_stream(handle_, static_cast<int>(N), current_t.data(), x0.data(), u0.data(), span));
+    }
+    else
+    {
+      std::vector<double> lo(limits.size() * MM, -INFINITY), up(limits.size() * MM, INFINITY);
+      for(size_t b = 0; b < limits.size(); b++)
+      {
+        for(int a = 0; a < MM && a < limits[b][0].size() && a < limits[b][1].size(); a++)
+        {
+          lo[b * MM + a] = limits[b][0][a];
+          up[b * MM + a] = limits[b][1][a];
+        }
+      }
+      nmpc_hip_ddp_stream_inputs in = {};
+      in.t0 = current_t.data();
+      in.x0 = x0.data();
+      in.u_init = u0.data();
+      in.params = problems.empty() ? nullptr : static_cast<const void *>(problems.data());
+      in.bytes_per_instance = sizeof(Problem);
+      in.lower = limits.empty() ? nullptr : lo.data();
+      in.upper = limits.empty() ? nullptr : up.data();
+      check(nmpc_hip_ddp_solve_stream_ex(handle_, static_cast<int>(N), &in, span));
+    }
     std::vector<double> X(N * (T + 1) * StateDim), U(N * T * MM), C(N * (T + 1));
     StreamResult r;
     r.status.resize(N);

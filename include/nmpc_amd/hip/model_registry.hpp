@@ -269,8 +269,8 @@ struct ModelOpsFor
     const int fan_auto = knobs.has_fan_auto ? knobs.fan_auto : kQuadFanOutAutoMaxIter;
     p.fan_out = p.family == Family::Quad && (cfg.line_search_fan_out == 1 || (cfg.line_search_fan_out == 0 && cfg.max_iter > fan_auto));
     // resumable launches (the ragged-convergence schedule, streamed solves): the quad kernel with the step-size-parallel line search
-    // and the two-wave kernel, one problem object for all instances
-    p.resumable = !own_problems && ((p.family == Family::Quad && (p.constrained || p.fan_out)) || p.family == Family::TwoWave);
+    // and the two-wave kernel, with one problem object for all instances or one per instance
+    p.resumable = (p.family == Family::Quad && (p.constrained || p.fan_out)) || p.family == Family::TwoWave;
     return p;
   }
   static size_t workspaceElems(const LaunchKnobs & knobs, int T)
@@ -415,6 +415,8 @@ struct ModelOpsFor
           const hipError_t e = requestDynamicLds<QuadSolver<Problem, false>>(
               {reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, false, false, true, true>),
                reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, true, false, true, true>),
+               reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, false, true, true, true>),
+               reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, true, true, true, true>),
                reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, false, false>),
                reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, true, false>),
                reinterpret_cast<const void *>(&ddp_solve_quad_kernel<Problem, false, true>),
@@ -427,7 +429,15 @@ struct ModelOpsFor
             return e;
           }
           const dim3 g(buf.Bp / kQuadInstances), blk(kQuadWaves * 64);
-          if(buf.iter_end > 0 && con) // (a resumable launch: shared problem object, plan.resumable)
+          if(buf.iter_end > 0 && own && con) // (a resumable launch, plan.resumable: one problem object per instance ...)
+          {
+            hipLaunchKernelGGL((ddp_solve_quad_kernel<Problem, true, true, true, true>), g, blk, lds, stream, problem, cfg, buf);
+          }
+          else if(buf.iter_end > 0 && own)
+          {
+            hipLaunchKernelGGL((ddp_solve_quad_kernel<Problem, false, true, true, true>), g, blk, lds, stream, problem, cfg, buf);
+          }
+          else if(buf.iter_end > 0 && con) // (... or the shared one)
           {
             hipLaunchKernelGGL((ddp_solve_quad_kernel<Problem, true, false, true, true>), g, blk, lds, stream, problem, cfg, buf);
           }
@@ -470,7 +480,15 @@ struct ModelOpsFor
           static_assert(lds <= 64 * 1024 && lds_con <= 64 * 1024,
                         "kTwoWaveFits keeps the records of both layouts within the default dynamic LDS limit");
           const dim3 g(buf.Bp / kLanesPerBlock), blk(2 * kLanesPerBlock);
-          if(buf.iter_end > 0 && con)
+          if(buf.iter_end > 0 && own && con)
+          {
+            hipLaunchKernelGGL((ddp_solve_tpi2w_kernel<Problem, true, true, true>), g, blk, lds_con, stream, problem, cfg, buf);
+          }
+          else if(buf.iter_end > 0 && own)
+          {
+            hipLaunchKernelGGL((ddp_solve_tpi2w_kernel<Problem, false, true, true>), g, blk, lds, stream, problem, cfg, buf);
+          }
+          else if(buf.iter_end > 0 && con)
           {
             hipLaunchKernelGGL((ddp_solve_tpi2w_kernel<Problem, true, false, true>), g, blk, lds_con, stream, problem, cfg, buf);
           }

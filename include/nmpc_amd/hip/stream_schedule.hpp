@@ -85,6 +85,9 @@ __global__ __launch_bounds__(256) void stream_extract_kernel(const DeviceBuffers
   {
     return; // empty, or still iterating
   }
+  // every thread has read id[p] and the resume word before thread 0 frees the slot at the end (both returns above are uniform
+  // per workgroup)
+  syncThreadsFuzzed(__LINE__);
   const int T = buf.T;
   const size_t rows_x = static_cast<size_t>(T + 1) * n, rows_u = static_cast<size_t>(T) * mm, rows_c = static_cast<size_t>(T + 1);
   const int sel = buf.sel[p];
@@ -183,6 +186,51 @@ __global__ __launch_bounds__(256) void stream_fill_kernel(const DeviceBuffers bu
       buf.resume[(tile * kResumeRows + 3) * 64 + ln] = 1.0;
       buf.resume[(tile * kResumeRows + 4) * 64 + ln] = 0.0;
       id[p] = q;
+    }
+  }
+}
+
+/** Per-instance problem objects and input limits of a heterogeneous queue (nmpc_hip_ddp_solve_stream_ex). */
+struct StreamOwn
+{
+  unsigned * params_slots; //!< [Bp][words] the per-slot problem objects the solve kernels read (DeviceBuffers::params_batch), or nullptr
+  const unsigned * params_queue; //!< [N][words] the queue's problem objects
+  const unsigned * params_shared; //!< [words] the handle's shared object: what an empty slot holds
+  int words; //!< sizeof(Problem) / 4
+  double * lim_slots; //!< [Bp][2][kMaxInputDim] the per-slot limits (DeviceBuffers::lim_batch), or nullptr
+  const double * lim_queue; //!< [N][2][kMaxInputDim]
+  const double * lim_shared; //!< [2][kMaxInputDim] the handle's shared limits (unbounded if it has none)
+};
+
+/** Beside stream_fill_kernel, with its decisions: slot p of [first, first + take) takes instance q's problem object and limits, every
+    other slot behind the dense prefix goes back to the shared ones — the lanes of empty slots construct their problem object too, so
+    every row holds a valid one at all times.  One workgroup per slot. */
+__global__ __launch_bounds__(64) void stream_fill_own_kernel(StreamOwn own, const int * __restrict__ w)
+{
+  const int p = blockIdx.x;
+  const int run = w[kSwRun], first = w[kSwFirst], prefix = w[kSwPrefix], cursor = w[kSwCursor];
+  if(p < run)
+  {
+    return; // in mid-solve
+  }
+  const bool fill = w[kSwTaken] > 0 && p >= first && p < prefix;
+  const size_t q = fill ? static_cast<size_t>(cursor + (p - first)) : 0;
+  if(own.params_slots)
+  {
+    const unsigned * src = fill ? own.params_queue + q * own.words : own.params_shared;
+    unsigned * dst = own.params_slots + static_cast<size_t>(p) * own.words;
+    for(int k = threadIdx.x; k < own.words; k += 64)
+    {
+      dst[k] = src[k];
+    }
+  }
+  if(own.lim_slots)
+  {
+    const double * src = fill ? own.lim_queue + q * 2 * kMaxInputDim : own.lim_shared;
+    double * dst = own.lim_slots + static_cast<size_t>(p) * 2 * kMaxInputDim;
+    for(int k = threadIdx.x; k < 2 * kMaxInputDim; k += 64)
+    {
+      dst[k] = src[k];
     }
   }
 }

@@ -90,8 +90,8 @@ extern "C"
        CUs a converged instance frees go to the batches behind it), off for the synchronous nmpc_hip_ddp_solve, for
        nmpc_hip_ddp_solve_device and for the ticks of nmpc_hip_ddp_mpc_run (max_iter is only a cap: a warm-started solve that
        converges within sixteen iterations must not pay the boundaries of the schedule, and a lone stream gains nothing from it);
-       1: on wherever supported (the quad and two-wave kernels with a shared problem object; what a pool of handles over
-       solve_device asks for), -1: off (one launch per solve). */
+       1: on wherever supported (the quad and two-wave kernels; what a pool of handles over solve_device asks for), -1: off (one
+       launch per solve).  Handles with per-instance problem objects (set_model_params_batch) run the schedule only under 1. */
     int ragged_schedule;
   } nmpc_hip_ddp_config;
 
@@ -324,9 +324,34 @@ extern "C"
       DDPSolver.hpp:26-141 once per instance, as a caller of the reference runs many problems through a few solver objects — and the
       slot of an instance that has finished takes the next one of the queue at the next round boundary (`span` iterations, 0: 8;
       include/nmpc_amd/hip/stream_schedule.hpp).  Every instance returns the bits of its lone solve on this kernel family.
-      Kernel families with resumable launches only (n <= 4, one input, fp64, shared problem object and limits); blocks until the
-      queue has drained.  Results: nmpc_hip_ddp_stream_get (X, U, COST, STATUS, ITERS, TRACE_LAST, DV; arrays of N instances). */
+      Kernel families with resumable launches only (n <= 4, one input, fp64); blocks until the queue has drained.  Every instance
+      solves the handle's problem object under the handle's limits here; nmpc_hip_ddp_solve_stream_ex takes a queue whose instances
+      bring their own.  Results: nmpc_hip_ddp_stream_get (X, U, COST, STATUS, ITERS, TRACE_LAST, DV; arrays of N instances). */
   int nmpc_hip_ddp_solve_stream(nmpc_hip_ddp_handle h, int n_instances, const double * t0, const double * x0, const double * u_init, int span);
+
+  /** Inputs of a heterogeneous queue (host arrays, reference layouts). */
+  typedef struct nmpc_hip_ddp_stream_inputs
+  {
+    const double * t0; /* [N] or NULL */
+    const double * x0; /* [N][n] */
+    const double * u_init; /* [N][T][MM] */
+    const void * params; /* [N] blobs of bytes_per_instance = param_bytes each, or NULL: the handle's shared object */
+    size_t bytes_per_instance;
+    const double * lower; /* [N][MM] constant-in-time limits per instance, or NULL (both or neither) */
+    const double * upper;
+  } nmpc_hip_ddp_stream_inputs;
+
+  /** nmpc_hip_ddp_solve_stream for a queue whose instances each have their own problem object and / or input limits — a caller of the
+      reference builds one DDPSolver per problem, each with its problem object and its setInputLimitsFunc, and runs them through its
+      cores (Monte-Carlo runs over model parameters, fleets of different robots, a target or weights per problem).  Instance q
+      solves params[q] (dt() and inputDim(t) as the handle's shared object: validated like nmpc_hip_ddp_set_model_params_batch, the
+      first offending index is named) within [lower[q], upper[q]]; the problem object and the limits travel with the instance into
+      whichever slot it takes, and every instance returns the bits of its lone solve (a plain handle with set_model_params_batch /
+      set_input_limits_batch).  params == NULL && lower == NULL: nmpc_hip_ddp_solve_stream, the same launches.  The per-slot arrays
+      belong to the call: afterwards the handle is what it was before, one problem object and one pair of limits for all.  Refused: a handle that carries
+      per-instance objects or limits of its own (NMPC_HIP_ERR_RUNTIME: those belong to slots, not to queue entries), lower without
+      upper, limits while with_input_constraint is off, time-varying limit tables, families without resumable launches. */
+  int nmpc_hip_ddp_solve_stream_ex(nmpc_hip_ddp_handle h, int n_instances, const nmpc_hip_ddp_stream_inputs * in, int span);
   int nmpc_hip_ddp_stream_get(nmpc_hip_ddp_handle h, int field, void * out, size_t bytes);
   /** Rounds of the last streamed solve and its device time (HIP events, input staging excluded) [msec]. */
   int nmpc_hip_ddp_last_stream_stats(nmpc_hip_ddp_handle h, int * rounds, float * ms);

@@ -511,7 +511,9 @@ bool raggedRounds(const nmpc_hip_ddp_solver * s, const KernelPlan & plan, std::v
   // [measured 858 -> 842 batch-iterations/s].  What gains is a caller with OTHER batches queued behind this one, so automatic
   // means: solves queued through nmpc_hip_ddp_solve_async (DDPSolverBatch::solveAsync, the C++ DDPSolverPool); synchronous solve(),
   // solve_device() and the ticks of mpc_run() take one launch.  Pools over solve_device ask with 1 (nmpc_amd.DDPSolverPool does).
-  if(mode == 0 && (!s->queued_solve || s->cfg.max_iter < 64))
+  // Per-instance problem objects: the schedule serves them only when asked for (1 / NMPC_HIP_DDP_RAGGED) — their resumable
+  // instantiations came later, and no call that used to take one launch takes several.
+  if(mode == 0 && (!s->queued_solve || s->cfg.max_iter < 64 || plan.own_problems))
   {
     return false;
   }
@@ -693,8 +695,10 @@ int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, con
 }
 
 /** A queue of n_total instances through the handle's B slots (stream_schedule.hpp).  in / out: device arrays in the reference
-    layouts.  span: iterations per round. */
-int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & plan, const nmpc_amd::hip::StreamArrays & io, int n_total, int span)
+    layouts.  span: iterations per round.  own: the queue's per-instance problem objects and / or limits (nmpc_hip_ddp_solve_stream_ex:
+    the handle's d_params_batch / d_lim_batch are the per-slot arrays for the time of the call), or nullptr. */
+int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & plan, const nmpc_amd::hip::StreamArrays & io, int n_total, int span,
+                 const nmpc_amd::hip::StreamOwn * own = nullptr)
 {
   using namespace nmpc_amd::hip;
   int rc = ensureRagged(s);
@@ -747,10 +751,20 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
   NMPC_HIP_TRY(hipEventRecord(ev0, st));
   hipLaunchKernelGGL(stream_begin_kernel, dim3(1), dim3(64), 0, st, w, n_total);
   NMPC_HIP_TRY(hipMemsetAsync(s->d_stream_id, 0xff, static_cast<size_t>(s->Bp) * sizeof(int), st)); // every slot empty (-1)
+  if(own)
+  {
+    // every one of the Bp rows starts with the shared problem object and limits (the words say "nothing filled yet"): the lanes of
+    // empty slots and of the padding construct their problem object like any other
+    hipLaunchKernelGGL(stream_fill_own_kernel, dim3(static_cast<unsigned>(s->Bp)), dim3(64), 0, st, *own, w);
+  }
   auto refill = [&]()
   {
     hipLaunchKernelGGL(stream_plan_kernel, dim3(1), dim3(64), 0, st, w, s->B);
     hipLaunchKernelGGL(stream_fill_kernel, fill_grid, dim3(256), 0, st, buf, io, s->d_stream_id, w, s->N, s->MM, s->d_t0, s->d_x0);
+    if(own)
+    {
+      hipLaunchKernelGGL(stream_fill_own_kernel, dim3(static_cast<unsigned>(s->B)), dim3(64), 0, st, *own, w);
+    }
   };
   refill();
   buf.stream_mode = 2; // a round: the workgroups of the region filled last start with the initial rollout, the others resume
@@ -1732,24 +1746,87 @@ extern "C"
 
   int nmpc_hip_ddp_solve_stream(nmpc_hip_ddp_handle s, int n_instances, const double * t0, const double * x0, const double * u_init, int span)
   {
-    if(!s || !x0 || !u_init || n_instances < 1)
+    nmpc_hip_ddp_stream_inputs in = {};
+    in.t0 = t0;
+    in.x0 = x0;
+    in.u_init = u_init;
+    return nmpc_hip_ddp_solve_stream_ex(s, n_instances, &in, span);
+  }
+
+  int nmpc_hip_ddp_solve_stream_ex(nmpc_hip_ddp_handle s, int n_instances, const nmpc_hip_ddp_stream_inputs * in, int span)
+  {
+    if(!s || !in || !in->x0 || !in->u_init || n_instances < 1)
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle, x0 or u_init, or no instances");
     }
-    if(s->cfg.with_input_constraint && !s->has_limits)
+    const double *t0 = in->t0, *x0 = in->x0, *u_init = in->u_init;
+    const bool own_params = in->params != nullptr, own_limits = in->lower != nullptr || in->upper != nullptr;
+    if((in->lower == nullptr) != (in->upper == nullptr))
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "only one of lower / upper given: per-instance limits need both, [N][input dimension] each");
+    }
+    if(own_limits && !s->cfg.with_input_constraint)
+    {
+      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "per-instance input limits were given but with_input_constraint is off: switch it on, or "
+                                                 "pass lower = upper = NULL");
+    }
+    if(s->cfg.with_input_constraint && !s->has_limits && !own_limits)
     {
       return fail(NMPC_HIP_ERR_RUNTIME, "with_input_constraint is set but no input limits were given "
                                         "(setInputLimitsFunc, DDPSolver.h:282-285)");
     }
-    const KernelPlan plan = planOf(s);
+    const KernelPlan plan = s->ops->plan(s->knobs, s->B, s->cfg, own_params || s->d_params_batch != nullptr);
     if(!plan.resumable)
     {
       return fail(NMPC_HIP_ERR_RUNTIME, "a streamed solve needs a kernel family with resumable launches: the quad / two-wave kernels "
-                                        "(n <= 4, one input, fp64) with a shared problem object");
+                                        "(n <= 4, one input, fp64)");
     }
-    if(s->d_lim_batch != nullptr || s->lim_steps_per_instance != 0 || s->d_lim_steps != nullptr)
+    if(s->d_params_batch != nullptr || s->d_lim_batch != nullptr)
     {
-      return fail(NMPC_HIP_ERR_RUNTIME, "a streamed solve takes input limits shared by all instances and constant along the horizon");
+      return fail(NMPC_HIP_ERR_RUNTIME, "the handle carries per-instance problem objects or limits (set_model_params_batch / "
+                                        "set_input_limits_batch): those belong to its slots, not to the instances of a queue.  Remove them "
+                                        "(NULL) and hand over the queue's own through nmpc_hip_ddp_solve_stream_ex "
+                                        "(nmpc_hip_ddp_stream_inputs::params, lower / upper)");
+    }
+    if(s->lim_steps_per_instance != 0 || s->d_lim_steps != nullptr)
+    {
+      return fail(NMPC_HIP_ERR_RUNTIME, "a streamed solve takes input limits constant along the horizon: shared by all instances, or one "
+                                        "pair per instance through nmpc_hip_ddp_solve_stream_ex");
+    }
+    const size_t pb = s->ops->param_bytes;
+    if(own_params)
+    {
+      // every blob is validated the way set_model_params_batch validates its own: dt() and inputDim(t) shape the batch
+      if(in->bytes_per_instance != pb)
+      {
+        return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "params size per instance should be " + std::to_string(pb) + " but "
+                                                       + std::to_string(in->bytes_per_instance) + ".");
+      }
+      const double dt_shared = s->ops->dt(s->params.data());
+      const unsigned char * src = static_cast<const unsigned char *>(in->params);
+      std::vector<int> dims_shared, dims;
+      for(int q = 0; q < n_instances; q++)
+      {
+        const unsigned char * blob = src + static_cast<size_t>(q) * pb;
+        if(s->ops->dt(blob) != dt_shared)
+        {
+          return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "instance " + std::to_string(q) + " of the queue has a different dt() than the "
+                                                         "handle's shared problem object");
+        }
+        if(s->ops->dynamic_input)
+        {
+          const double tq = t0 ? t0[q] : 0.0;
+          dims_shared.resize(static_cast<size_t>(s->T));
+          dims.resize(static_cast<size_t>(s->T));
+          s->ops->input_dims(s->params.data(), tq, s->T, dims_shared.data());
+          s->ops->input_dims(blob, tq, s->T, dims.data());
+          if(dims != dims_shared)
+          {
+            return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "instance " + std::to_string(q) + " of the queue has other inputDim(t) than the "
+                                                           "handle's shared problem object");
+          }
+        }
+      }
     }
     if(span <= 0)
     {
@@ -1757,10 +1834,13 @@ extern "C"
     }
     NMPC_HIP_TRY(hipSetDevice(s->device));
     NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
+    constexpr size_t kLim = 2 * nmpc_amd::hip::kMaxInputDim; // doubles of one limits row
     const size_t N = static_cast<size_t>(n_instances), T = static_cast<size_t>(s->T), n = static_cast<size_t>(s->N), mm = static_cast<size_t>(s->MM);
     const size_t n_t0 = N, n_x0 = N * n, n_u = N * T * mm, n_X = N * (T + 1) * n, n_c = N * (T + 1), n_tr = N * NMPC_HIP_NTRACE, n_dv = N * 2;
-    const size_t doubles = n_t0 + n_x0 + n_u + n_X + n_u + n_c + n_tr + n_dv;
-    const size_t bytes = doubles * sizeof(double) + 2 * N * sizeof(int);
+    // (the queue's limits and problem objects, each followed by the shared row that empty slots hold)
+    const size_t n_lim = own_limits ? (N + 1) * kLim : 0, param_bytes_staged = own_params ? (N + 1) * pb : 0;
+    const size_t doubles = n_t0 + n_x0 + n_u + n_X + n_u + n_c + n_tr + n_dv + n_lim;
+    const size_t bytes = doubles * sizeof(double) + 2 * N * sizeof(int) + param_bytes_staged;
     if(bytes > s->stream_io_bytes)
     {
       if(s->d_stream_io)
@@ -1786,15 +1866,84 @@ extern "C"
     io.cost = io.U + n_u;
     io.trace_last = io.cost + n_c;
     io.dV = io.trace_last + n_tr;
-    io.status = reinterpret_cast<int *>(io.dV + n_dv);
+    double * d_lim_queue = io.dV + n_dv;
+    io.status = reinterpret_cast<int *>(d_lim_queue + n_lim);
     io.iters = io.status + N;
+    unsigned char * d_params_queue = reinterpret_cast<unsigned char *>(io.iters + N); // (8-byte aligned: 2 N ints behind doubles)
     if(t0)
     {
       NMPC_HIP_TRY(hipMemcpyAsync(d_t0, t0, n_t0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
     }
     NMPC_HIP_TRY(hipMemcpyAsync(d_x0, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
     NMPC_HIP_TRY(hipMemcpyAsync(d_u, u_init, n_u * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    int rc = launchStream(s, s->stream, plan, io, n_instances, span);
+    if(!own_params && !own_limits)
+    {
+      int rc = launchStream(s, s->stream, plan, io, n_instances, span);
+      if(rc != NMPC_HIP_OK)
+      {
+        return rc;
+      }
+      s->stream_arrays = io;
+      s->stream_n = n_instances;
+      s->solved = true;
+      return NMPC_HIP_OK;
+    }
+    // A heterogeneous queue.  The per-slot arrays [Bp][sizeof(Problem)] / [Bp][2][kMaxInputDim] belong to this call: they are the
+    // handle's d_params_batch / d_lim_batch while it runs (the launches and the compaction's swap table find them there), and the
+    // handle is back to its shared problem object and limits on every way out.
+    std::vector<double> h_lim; // (outlives the copies queued from it: the guard below waits for the stream first)
+    struct SlotArrays
+    {
+      nmpc_hip_ddp_solver * s;
+      bool had_limits;
+      ~SlotArrays()
+      {
+        (void)hipStreamSynchronize(s->stream);
+        if(s->d_params_batch)
+        {
+          (void)hipFree(s->d_params_batch);
+          s->d_params_batch = nullptr;
+        }
+        if(s->d_lim_batch)
+        {
+          (void)hipFree(s->d_lim_batch);
+          s->d_lim_batch = nullptr;
+        }
+        s->has_limits = had_limits;
+      }
+    } slots{s, s->has_limits};
+    nmpc_amd::hip::StreamOwn own = {};
+    if(own_params)
+    {
+      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_params_batch), static_cast<size_t>(s->Bp) * pb));
+      NMPC_HIP_TRY(hipMemcpyAsync(d_params_queue, in->params, N * pb, hipMemcpyHostToDevice, s->stream));
+      NMPC_HIP_TRY(hipMemcpyAsync(d_params_queue + N * pb, s->params.data(), pb, hipMemcpyHostToDevice, s->stream));
+      own.params_slots = reinterpret_cast<unsigned *>(s->d_params_batch);
+      own.params_queue = reinterpret_cast<const unsigned *>(d_params_queue);
+      own.params_shared = reinterpret_cast<const unsigned *>(d_params_queue + N * pb);
+      own.words = static_cast<int>(pb / sizeof(unsigned));
+    }
+    if(own_limits)
+    {
+      constexpr int kMax = nmpc_amd::hip::kMaxInputDim;
+      h_lim.resize(n_lim);
+      for(size_t q = 0; q <= N; q++) // (row N: the shared limits — unbounded if the handle was given none)
+      {
+        for(int a = 0; a < kMax; a++)
+        {
+          const bool given = q < N && a < s->MM;
+          h_lim[(q * 2 + 0) * kMax + a] = given ? in->lower[q * mm + a] : (q < N ? -INFINITY : s->lim_lo[a]);
+          h_lim[(q * 2 + 1) * kMax + a] = given ? in->upper[q * mm + a] : (q < N ? INFINITY : s->lim_hi[a]);
+        }
+      }
+      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_batch), static_cast<size_t>(s->Bp) * kLim * sizeof(double)));
+      NMPC_HIP_TRY(hipMemcpyAsync(d_lim_queue, h_lim.data(), n_lim * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      own.lim_slots = s->d_lim_batch;
+      own.lim_queue = d_lim_queue;
+      own.lim_shared = d_lim_queue + N * kLim;
+      s->has_limits = true;
+    }
+    int rc = launchStream(s, s->stream, plan, io, n_instances, span, &own);
     if(rc != NMPC_HIP_OK)
     {
       return rc;

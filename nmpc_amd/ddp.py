@@ -280,8 +280,10 @@ class DDPSolverBatch:
                 _capi.check(self._L.nmpc_hip_ddp_set_model_params_batch(self._h, raw, nb))
             self._problem_batch_dirty = False
         c = self._config.to_c()
-        if getattr(self, "_pooled", False) and c.ragged_schedule == 0:
-            c.ragged_schedule = 1  # a pool's handle has other batches queued behind this one: "automatic" means on (where supported)
+        if getattr(self, "_pooled", False) and c.ragged_schedule == 0 and getattr(self, "_problem_batch", None) is None:
+            # a pool's handle has other batches queued behind this one: "automatic" means on (where supported; a handle with one
+            # problem object per instance runs the schedule only when asked for, as under nmpc_hip_ddp_solve_async)
+            c.ragged_schedule = 1
         _capi.check(self._L.nmpc_hip_ddp_set_config(self._h, C.byref(c)))
         if self._limits is not None:
             lo, up = self._limits
@@ -378,12 +380,16 @@ class DDPSolverBatch:
         return status == 1
 
     # ---- a queue of instances through the handle's slots (nmpc_hip_ddp_solve_stream; round 6) ----
-    def solveStream(self, current_t, current_x, initial_u_list, span: int = 0) -> "StreamResult":
+    def solveStream(self, current_t, current_x, initial_u_list, span: int = 0, problems: Optional[Sequence[_Problem]] = None,
+                    input_limits=None) -> "StreamResult":
         """N >> batch_size instances (current_t: scalar or (N,), current_x: (N, n), initial_u_list: (N, T, MM)), each solved to ITS
         convergence as DDPSolver::solve would (DDPSolver.hpp:26-141): batch_size slots, and the slot of an instance that has finished
         takes the next one of the queue after at most `span` (0: 8) further iterations of its neighbours
         (include/nmpc_amd/hip/stream_schedule.hpp).  Every instance returns the bits of its lone solve on the same kernel family.
-        Kernel families with resumable launches only (n <= 4, one input, fp64; shared problem object and limits)."""
+        Kernel families with resumable launches only (n <= 4, one input, fp64).
+        problems: N problem objects of the handle's type, one per instance of the queue (dt and inputDim(t) as the shared one);
+        input_limits: (lower, upper) of shape (N, MM), constant in time, one pair per instance (nmpc_hip_ddp_solve_stream_ex).
+        Without either every instance solves the handle's problem under the handle's limits."""
         x0 = np.ascontiguousarray(np.asarray(current_x, dtype=np.float64))
         if x0.ndim != 2 or x0.shape[1] != self.n:
             raise ValueError("current_x should be (N, %d)" % self.n)
@@ -394,7 +400,28 @@ class DDPSolverBatch:
         T = int(self._config.horizon_steps)
         u = np.ascontiguousarray(np.asarray(initial_u_list, dtype=np.float64).reshape(N, T, self.mm))
         dp = C.POINTER(C.c_double)
-        _capi.check(self._L.nmpc_hip_ddp_solve_stream(self._h, N, t0.ctypes.data_as(dp), x0.ctypes.data_as(dp), u.ctypes.data_as(dp), int(span)))
+        if problems is None and input_limits is None:
+            _capi.check(self._L.nmpc_hip_ddp_solve_stream(self._h, N, t0.ctypes.data_as(dp), x0.ctypes.data_as(dp), u.ctypes.data_as(dp), int(span)))
+        else:
+            inp = _capi.StreamInputs()
+            inp.t0, inp.x0, inp.u_init = t0.ctypes.data_as(dp), x0.ctypes.data_as(dp), u.ctypes.data_as(dp)
+            keep = []  # (the buffers the struct points into)
+            if problems is not None:
+                problems = list(problems)
+                if len(problems) != N:
+                    raise ValueError(f"problems should be {N} but {len(problems)}.")
+                raw = C.create_string_buffer(b"".join(bytes(p.blob) for p in problems))
+                keep.append(raw)
+                inp.params = C.cast(raw, C.c_void_p)
+                inp.bytes_per_instance = C.sizeof(problems[0].blob)
+            if input_limits is not None:
+                lower, upper = input_limits
+                for name, v in (("lower", lower), ("upper", upper)):
+                    if v is not None:
+                        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(N, self.mm))
+                        keep.append(a)
+                        setattr(inp, name, a.ctypes.data_as(dp))
+            _capi.check(self._L.nmpc_hip_ddp_solve_stream_ex(self._h, N, C.byref(inp), int(span)))
         self._cache = {}
 
         def get(field, dtype, shape):
