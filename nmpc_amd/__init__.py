@@ -9,3 +9,4 @@ from .models import (DDPProblemBipedal, DDPProblemCartPole, DDPProblemCartPoleF3
                      DDPProblemManipulator, DDPProblemManipulatorF32, DDPProblemQuadrotor, DDPProblemVerticalMotion, make_problem)
 from .cgmres import CgmresProblem, CgmresProblemCartPole, CgmresProblemSemiactiveDamper, CgmresSolverBatch  # noqa: F401
 from .boxqp import BoxQPBatch  # noqa: F401
+from .riccati import RiccatiBatch  # noqa: F401
