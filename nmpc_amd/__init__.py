@@ -10,3 +10,4 @@ from .models import (DDPProblemBipedal, DDPProblemCartPole, DDPProblemCartPoleF3
 from .cgmres import CgmresProblem, CgmresProblemCartPole, CgmresProblemSemiactiveDamper, CgmresSolverBatch  # noqa: F401
 from .boxqp import BoxQPBatch  # noqa: F401
 from .riccati import RiccatiBatch  # noqa: F401
+from .fmpc_step import FmpcStepBatch  # noqa: F401

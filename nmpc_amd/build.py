@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libnmpc_hip_ddp.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ("capi.hip", "builtin_models.hip", "model_centroidal.hip", "model_quadrotor.hip", "model_manipulator.hip",
            "model_quadrotor_f32.hip", "model_cartpole_f32.hip", "model_manipulator_f32.hip", "model_planar_vtol.hip", "fmpc_capi.hip", "fmpc_models.hip", "fmpc_models_dynamic.hip",
-           "cgmres_capi.hip", "cgmres_models.hip", "cgmres_wave_models.hip", "boxqp_capi.hip", "gmres_capi.hip", "riccati_capi.hip")
+           "cgmres_capi.hip", "cgmres_models.hip", "cgmres_wave_models.hip", "boxqp_capi.hip", "gmres_capi.hip", "riccati_capi.hip", "fmpc_step_capi.hip")
 ARCH = "gfx950"
 # per-source flags.  builtin_models.hip holds the quad kernel (ddp_kernels_quad.hpp): its fp64 matrix-core results are
 # consumed by VALU / DPP instructions right away, so they have to live in ordinary VGPRs — by default a kernel that may
@@ -30,7 +30,8 @@ EXTRA_FLAGS = {"builtin_models.hip": ["-mllvm", "--amdgpu-mfma-vgpr-form"],
                "cgmres_capi.hip": ["-ffp-contract=off"], "cgmres_models.hip": ["-ffp-contract=off"],
                "cgmres_wave_models.hip": ["-ffp-contract=off"],  # the wave kernels return the lane kernels' bits
                "gmres_capi.hip": ["-ffp-contract=off"],  # batched GMRES: the same, against tests/cpp/gmres_checker.cpp
-               "riccati_capi.hip": ["-ffp-contract=off"]}  # batched Riccati pass: the same, against tests/cpp/riccati_checker.cpp
+               "riccati_capi.hip": ["-ffp-contract=off"],  # batched Riccati pass: the same, against tests/cpp/riccati_checker.cpp
+               "fmpc_step_capi.hip": ["-ffp-contract=off"]}  # batched FMPC iteration: the same, against tests/cpp/fmpc_step_checker.cpp
 
 
 def hipcc() -> str:
@@ -40,7 +41,7 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found: the MI355X path cannot be built (there is no CPU fallback)")
 
 
-HOST_ONLY_HEADERS = ("DDPSolverBatch.hpp", "DDPSolverSharded.hpp", "FmpcSolverBatch.hpp", "CgmresSolverBatch.hpp", "BoxQPBatch.hpp", "GmresBatch.hpp", "RiccatiBatch.hpp")  # mirrors over the C-ABI: no translation unit of the library includes them
+HOST_ONLY_HEADERS = ("DDPSolverBatch.hpp", "DDPSolverSharded.hpp", "FmpcSolverBatch.hpp", "CgmresSolverBatch.hpp", "BoxQPBatch.hpp", "GmresBatch.hpp", "RiccatiBatch.hpp", "FmpcStepBatch.hpp")  # mirrors over the C-ABI: no translation unit of the library includes them
 
 
 def _headers():
