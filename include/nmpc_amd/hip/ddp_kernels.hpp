@@ -96,6 +96,13 @@ struct DeviceBuffersT
   //                  to its max_iter-th.
   int stream_mode = 0;
   const int * first_active = nullptr; //!< device word (stream_mode 1), or nullptr: 0
+  // ---- the caller's arrays in the reference layouts, for the launch that converts them itself (the quad kernel's whole-solve
+  // launch: QuadSolver::ingestInputs writes t0, x0 and half 0 of U as ingest_kernel does, ahead of the initial rollout).  All
+  // nullptr on every other path: the handle's arrays were filled before the launch.  They are inputs only and have to stay
+  // valid until the solve has run.
+  const double * in_t0 = nullptr; //!< current_t [B], or nullptr: zeros
+  const double * in_x0 = nullptr; //!< current_x [B][N]; nullptr: no conversion in the solve kernel
+  const double * in_u = nullptr; //!< initial_u_list [B][T * MM]
 };
 constexpr int kResumeRows = 5;
 /** The reference computes in double (DDPProblem.h:20-35): every kernel but the fp32 tile kernel uses this one. */

@@ -744,6 +744,94 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       }
     }
   }
+
+  // ---- the caller's inputs, converted by the workgroup itself (DeviceBuffers::in_x0 set: whole-solve launches) ----
+  static constexpr int kIngestRows = 32; //!< rows of U per batch of one wavefront: 16 instances x 32 rows = 8 loads per lane
+  static constexpr int kIngestLoads = kQuadInstances * kIngestRows / 64;
+  static constexpr int kIngestPitch = kQuadInstances + 1; //!< doubles per staged row: odd, the 32 rows of a write land in 32 banks
+  static_assert(kIngestRows * kIngestPitch <= kChunkDoubles, "the staging area is a wave's derivative chunk");
+  /** What ingest_kernel (ddp_kernels.hpp) writes for the 16 lanes of this workgroup, `b0` the first of them: t0 (zeros without
+      in_t0), the x0 rows, half 0 of the U rows — zeros for the instances beyond B, which go on computing on them.  Every wave of the
+      workgroup calls it ahead of the first pass, and a fullBarrier() behind it makes the rows visible to all four.
+      The caller's rows of 16 consecutive instances are read along the rows: a wave takes batches of 32 rows x 16 instances (256
+      contiguous bytes per instance and load instruction), all eight loads requested before the first use, turns them through its
+      own derivative chunk — idle until the first backward pass, wave-private, so LDS program order is all the ordering it needs —
+      and writes along the lanes: 128 contiguous bytes per row.  On the master's rollout chain the same data would be one
+      ~20-cycle global_load per timestep on a lone wave, uncoalesced across the lanes.
+      Not inlined, as PairSolver::copyRows: the passes behind it are sensitive to register allocation.  Behind the call boundary
+      the pointers are generic ones, so their address spaces are named again: global_load / ds_write with a counter each, not
+      flat accesses that wait on both. */
+  using GlobalIn = const double __attribute__((address_space(1))) *;
+  using GlobalOut = double __attribute__((address_space(1))) *;
+  using LdsPtr = double __attribute__((address_space(3))) *;
+  __device__ __attribute__((noinline)) static void ingestInputs(const double * in_t0,
+                                                                const double * in_x0,
+                                                                const double * in_u,
+                                                                double * t0,
+                                                                double * x0,
+                                                                double * U,
+                                                                int B,
+                                                                int RU,
+                                                                int b0,
+                                                                double * stage_generic)
+  {
+    GlobalIn g_t0 = (GlobalIn)in_t0, g_x0 = (GlobalIn)in_x0, g_u = (GlobalIn)in_u;
+    LdsPtr stage = (LdsPtr)stage_generic;
+    const int wave_i = threadIdx.x / 64, l = threadIdx.x % 64;
+    const size_t tile_i = static_cast<size_t>(b0) / LW;
+    const int lane0 = b0 % static_cast<int>(LW);
+    GlobalOut u_out = (GlobalOut)(U + tile_i * 2 * static_cast<size_t>(RU) * LW + lane0); // half 0
+    for(int r0 = wave_i * kIngestRows; r0 < RU; r0 += kQuadWaves * kIngestRows)
+    {
+      double v[kIngestLoads];
+      const int rr = l % kIngestRows, r = r0 + rr;
+      NMPC_UNROLL
+      for(int k = 0; k < kIngestLoads; k++)
+      {
+        const int bb = b0 + k * (64 / kIngestRows) + l / kIngestRows;
+        const bool ok = bb < B && r < RU;
+        v[k] = g_u[ok ? static_cast<size_t>(bb) * RU + r : 0]; // (element 0 exists: the loads stay unconditional, one batch)
+        v[k] = ok ? v[k] : 0.0;
+      }
+      NMPC_UNROLL
+      for(int k = 0; k < kIngestLoads; k++)
+      {
+        stage[rr * kIngestPitch + k * (64 / kIngestRows) + l / kIngestRows] = v[k];
+      }
+      asm volatile("" ::: "memory"); // (written by other lanes of this wave: LDS is in order)
+      NMPC_UNROLL
+      for(int k = 0; k < kIngestLoads; k++)
+      {
+        const int rw = k * (64 / kQuadInstances) + l / kQuadInstances;
+        v[k] = stage[rw * kIngestPitch + l % kQuadInstances];
+      }
+      NMPC_UNROLL
+      for(int k = 0; k < kIngestLoads; k++)
+      {
+        const int rw = r0 + k * (64 / kQuadInstances) + l / kQuadInstances;
+        if(rw < RU)
+        {
+          u_out[static_cast<size_t>(rw) * LW + l % kQuadInstances] = v[k];
+        }
+      }
+      asm volatile("" ::: "memory"); // (the next batch's writes stay behind these reads)
+    }
+    if(wave_i == kQuadWaves - 1) // (the wave with the shortest share of U at the headline horizon)
+    {
+      for(int e = l; e < kQuadInstances * N; e += 64)
+      {
+        const int inst = e / N, j = e % N;
+        const bool ok = b0 + inst < B;
+        const double xv = g_x0[ok ? static_cast<size_t>(b0) * N + e : 0];
+        ((GlobalOut)x0)[tile_i * N * LW + static_cast<size_t>(j) * LW + lane0 + inst] = ok ? xv : 0.0;
+      }
+    }
+    else if(wave_i == kQuadWaves - 2 && l < kQuadInstances)
+    {
+      const bool ok = in_t0 != nullptr && b0 + l < B;
+      ((GlobalOut)t0)[tile_i * LW + lane0 + l] = ok ? g_t0[b0 + l] : 0.0;
+    }
+  }
 };
 
 /** The quad solve kernel: grid = Bp / 16 workgroups of 256 threads.  Compile the translation unit with
@@ -782,6 +870,17 @@ __global__ __launch_bounds__(kQuadWaves * 64) void ddp_solve_quad_kernel(const P
   const Problem mine_lin = kOwnProblem ? instanceProblem(problem, buf, b_lin) : problem;
   Solver solver(mine, kOwnProblem ? mine_lin : mine, cfg, buf, b, lds_quad);
   solver.stream_fresh_wg = solver_fresh;
+  if constexpr(!kResumable)
+  {
+    // a whole solve in one dispatch: the workgroup converts its instances' inputs itself (no ingest_kernel ahead of this launch).
+    // Master and followers read t0 behind the barrier (solveMasterWith / solveMasterFanOut, below).
+    if(buf.in_x0 != nullptr)
+    {
+      Solver::ingestInputs(buf.in_t0, buf.in_x0, buf.in_u, const_cast<double *>(buf.t0), const_cast<double *>(buf.x0), buf.U, buf.B, buf.T * Solver::MM,
+                           static_cast<int>(blockIdx.x) * kQuadInstances, solver.chunk);
+      fullBarrier();
+    }
+  }
   if(threadIdx.x / 64 == 0)
   {
     if constexpr(kResumable)

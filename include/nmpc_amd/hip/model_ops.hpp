@@ -71,7 +71,8 @@ inline bool familyByName(const char * name, Family * out)
 /** What picks a kernel family and its launch schedule besides the problem's shape, the batch size and the Configuration — per
     HANDLE, fixed when the handle is created or through the C-ABI (nmpc_hip_ddp_set_kernel, nmpc_hip_ddp_set_dispatch_batch), never
     read from the environment on the launch path.  The environment variables (NMPC_HIP_DDP_KERNEL, NMPC_HIP_DDP_TILE64_GROUP / _CHUNK /
-    _PAIR / _ADOPT / _WIDE, NMPC_HIP_DDP_FAN_SCRATCH, NMPC_HIP_DDP_FAN_AUTO, NMPC_HIP_DDP_RAGGED, NMPC_HIP_DDP_NO_WORKSPACE) are
+    _PAIR / _ADOPT / _WIDE, NMPC_HIP_DDP_FAN_SCRATCH, NMPC_HIP_DDP_FAN_AUTO, NMPC_HIP_DDP_RAGGED, NMPC_HIP_DDP_NO_WORKSPACE,
+    NMPC_HIP_DDP_FUSED_INGEST) are
     developer overrides for A/B measurements and tests: fromEnvironment() reads them ONCE, when a handle is created. */
 struct LaunchKnobs
 {
@@ -88,6 +89,9 @@ struct LaunchKnobs
   //! > 0: the batch size the kernel family is chosen FOR — a shard of a larger solve takes the family the whole batch would get,
   //! so that its results are the unsharded solve's bit for bit (families differ in the last bits; DDPSolverSharded, bench.py)
   int dispatch_batch = 0;
+  //! 1: a whole-solve launch of the quad kernel reads the caller's arrays itself (QuadSolver::ingestInputs) — one dispatch per
+  //! solve_device, no ingest_kernel and no event between the two; 0: ingest_kernel first, as every other family (A/B, tests)
+  int fused_ingest = 1;
 
   int batchFor(int batch) const
   {
@@ -143,6 +147,10 @@ struct LaunchKnobs
     {
       k.have_workspace = std::strcmp(e, "0") == 0;
     }
+    if(const char * e = std::getenv("NMPC_HIP_DDP_FUSED_INGEST"))
+    {
+      k.fused_ingest = std::strcmp(e, "0") != 0;
+    }
     return k;
   }
 };
@@ -176,7 +184,7 @@ struct KernelPlan
 };
 
 //! bumped whenever ModelOps changes layout: nmpc_hip_ddp_register_model refuses a table compiled against another header
-constexpr int kModelOpsAbi = 2;
+constexpr int kModelOpsAbi = 3;
 
 /** Type-erased operations of one registered problem type. */
 struct ModelOps

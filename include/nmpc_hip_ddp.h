@@ -209,7 +209,10 @@ extern "C"
   int nmpc_hip_ddp_solve_async(nmpc_hip_ddp_handle h, const double * t0, const double * x0, const double * u_init);
 
   /** Same with DEVICE pointers (reference layouts above, resident in HBM), asynchronous on `stream`
-      (a hipStream_t, NULL = the solver's own stream).  Nothing is copied over PCIe. */
+      (a hipStream_t, NULL = the solver's own stream).  Nothing is copied over PCIe.
+      The three arrays are inputs only and must stay valid, and unchanged, until the solve has RUN (not merely until this call
+      returns): they are read by work queued on `stream` — a conversion kernel ahead of the solve, or the solve kernel itself
+      (cart-pole / bipedal up to 4096 instances: one dispatch per solve). */
   int nmpc_hip_ddp_solve_device(nmpc_hip_ddp_handle h,
                                 const double * d_t0,
                                 const double * d_x0,

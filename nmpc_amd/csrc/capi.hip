@@ -91,6 +91,7 @@ struct nmpc_hip_ddp_solver
   static constexpr int kEvPool = 128;
   hipEvent_t ev_begin[kEvPool] = {}, ev_kernel[kEvPool] = {}, ev_end[kEvPool] = {};
   bool ev_pending[kEvPool] = {};
+  bool ev_fused[kEvPool] = {}; // the slot's solve was ONE dispatch (launchRecorded: the quad kernel read the caller's arrays): no ev_kernel
   long long n_solves = 0; // solves recorded since create / last reset
   long long n_harvested = 0;
   double sum_total_ms = 0, sum_kernel_ms = 0;
@@ -438,7 +439,14 @@ int harvestSlot(nmpc_hip_ddp_solver * s, int slot)
   NMPC_HIP_TRY(hipEventSynchronize(s->ev_end[slot]));
   float tot = 0, ker = 0;
   NMPC_HIP_TRY(hipEventElapsedTime(&tot, s->ev_begin[slot], s->ev_end[slot]));
-  NMPC_HIP_TRY(hipEventElapsedTime(&ker, s->ev_kernel[slot], s->ev_end[slot]));
+  if(s->ev_fused[slot])
+  {
+    ker = tot; // the conversion is part of the solve kernel: begin -> end
+  }
+  else
+  {
+    NMPC_HIP_TRY(hipEventElapsedTime(&ker, s->ev_kernel[slot], s->ev_end[slot]));
+  }
   s->sum_total_ms += tot;
   s->sum_kernel_ms += ker;
   s->last_total_ms = tot;
@@ -864,14 +872,18 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
 
 /** One solve on stream st, bracketed by the HIP-event triple of the timing ring.  ingest: convert the reference-layout
     device arrays into the solver's tile-major input buffers first (false: they are already in place, as after
-    mpc_advance_kernel). */
+    mpc_advance_kernel).  may_fuse: the solve may be ONE dispatch — when it is a whole-solve launch of the quad kernel in fp64, the
+    kernel's workgroups convert their own instances' inputs (QuadSolver::ingestInputs) and the stream sees event, kernel, event instead
+    of event, ingest_kernel, event, kernel, event.  Ragged rounds, the other families, fp32 and LaunchKnobs::fused_ingest = 0 keep
+    ingest_kernel. */
 int launchRecorded(nmpc_hip_ddp_solver * s,
                    hipStream_t st,
                    const double * d_t0,
                    const double * d_x0,
                    const double * d_u_init,
                    bool ingest,
-                   bool timed = true)
+                   bool timed = true,
+                   bool may_fuse = false)
 {
   // timed = false: no event records around this solve (the inner ticks of the device-resident receding-horizon loop: three
   // event packets per 0.6 ms tick were 1 - 2 % of the loop; computationDuration() reports the loop's last solve)
@@ -887,7 +899,10 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
     }
     NMPC_HIP_TRY(hipEventRecord(s->ev_begin[slot], st));
   }
-  if(ingest)
+  std::vector<int> caps;
+  bool whole_solve = !raggedRounds(s, plan, &caps);
+  const bool fused = ingest && may_fuse && whole_solve && plan.family == nmpc_amd::hip::Family::Quad && s->elem == 8 && s->knobs.fused_ingest != 0;
+  if(ingest && !fused)
   {
     // reference layouts -> instance-minor device layout, one launch
     const int RU = s->T * s->MM;
@@ -906,13 +921,21 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
   }
   if(timed)
   {
-    NMPC_HIP_TRY(hipEventRecord(s->ev_kernel[slot], st));
+    s->ev_fused[slot] = fused;
+    if(!fused)
+    {
+      NMPC_HIP_TRY(hipEventRecord(s->ev_kernel[slot], st));
+    }
   }
   DeviceBuffers buf = makeBuffers(s);
-  std::vector<int> caps;
+  if(fused)
+  {
+    buf.in_t0 = d_t0;
+    buf.in_x0 = d_x0;
+    buf.in_u = d_u_init;
+  }
   s->last_gain_layout = plan.gainLayout();
   s->last_ragged_rounds = 1;
-  bool whole_solve = !raggedRounds(s, plan, &caps);
   if(!whole_solve)
   {
     int rrc = launchRagged(s, st, buf, plan, caps, &whole_solve);
@@ -1513,7 +1536,7 @@ extern "C"
     }
     NMPC_HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    return launchRecorded(s, st, d_t0, d_x0, d_u_init, true);
+    return launchRecorded(s, st, d_t0, d_x0, d_u_init, true, true, true);
   }
 
   int nmpc_hip_ddp_mpc_default_options(nmpc_hip_ddp_mpc_options * opt)
