@@ -103,7 +103,8 @@ extern "C"
       min_step 1e-22, armijo_param 0.1; trace_capacity 0. */
   int nmpc_hip_boxqp_default_config(nmpc_hip_boxqp_config * cfg);
 
-  /** BoxQP(var_dim) (BoxQP.h:101-118) for `batch` QPs on HIP device `device`; 1 <= var_dim <= 64, batch >= 1. */
+  /** BoxQP(var_dim) (BoxQP.h:101-118) for `batch` QPs on HIP device `device`; 1 <= var_dim <= 64, batch >= 1.  An allocation that
+      fails, here or in a later call, is NMPC_HIP_ERR_RUNTIME with the byte count in the message. */
   int nmpc_hip_boxqp_create(int var_dim, int batch, int device, nmpc_hip_boxqp_handle * out);
   int nmpc_hip_boxqp_destroy(nmpc_hip_boxqp_handle h);
 

@@ -10,7 +10,9 @@
 #include <vector>
 
 #include <nmpc_amd/hip/boxqp_kernels.hpp>
+#include <nmpc_amd/hip/capi_core.hpp>
 
+namespace capi = nmpc_amd::hip::capi;
 namespace bq = nmpc_amd::hip::boxqp;
 
 static_assert(NMPC_HIP_BOXQP_MAX_DIM == bq::kMaxDim && NMPC_HIP_BOXQP_LANE_MAX_DIM == bq::kLaneMaxDim
@@ -19,40 +21,13 @@ static_assert(NMPC_HIP_BOXQP_MAX_DIM == bq::kMaxDim && NMPC_HIP_BOXQP_LANE_MAX_D
 
 namespace
 {
-thread_local std::string g_boxqp_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family
 {
-  g_boxqp_last_error = msg;
-  return code;
-}
-
-#define BQ_TRY(expr)                                                                      \
-  do                                                                                      \
-  {                                                                                       \
-    hipError_t e_ = (expr);                                                               \
-    if(e_ != hipSuccess)                                                                  \
-    {                                                                                     \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    }                                                                                     \
-  } while(0)
-
-int checkDevice(int device)
-{
-  int n_dev = 0;
-  const hipError_t e = hipGetDeviceCount(&n_dev);
-  if(e != hipSuccess || n_dev <= 0)
-  {
-    return fail(NMPC_HIP_ERR_NO_DEVICE, std::string("no HIP device available (") + hipGetErrorString(e) +
-                                            "): the BoxQP solver has no CPU fallback");
-  }
-  if(device < 0 || device >= n_dev)
-  {
-    return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
-  }
-  BQ_TRY(hipSetDevice(device));
-  return NMPC_HIP_OK;
-}
+  static constexpr const char * tag = "[BoxQP]";
+  static constexpr const char * noun = "the BoxQP solver";
+  static constexpr const char * prefix = "nmpc_hip_boxqp";
+};
+constexpr auto fail = capi::fail<Family>;
 
 enum Kernel
 {
@@ -68,43 +43,28 @@ Kernel autoKernel(int var_dim, int batch)
 }
 } // namespace
 
-struct nmpc_hip_boxqp_solver
+struct nmpc_hip_boxqp_solver : capi::HandleCore<Family>
 {
   int n = 0;
   size_t B = 0;
-  int device = 0;
   nmpc_hip_boxqp_config cfg;
   Kernel pinned = kAuto;
   Kernel last = kAuto; // the kernel of the last solve (-1: none yet)
-  std::vector<void *> allocs;
   // results, boundary layout
   double * d_x = nullptr; // [B][n]
   double * d_factor = nullptr; // [B][n][n]
   bq::Results res{};
-  void * d_trace = nullptr;
+  void * d_trace = nullptr; // not one of allocs: set_config frees and reallocates it
   // lane kernel: inputs, workspace and results [element][instance] (allocated for n <= 16)
   bq::LaneBuffers lane{};
   double *lane_H = nullptr, *lane_g = nullptr, *lane_lower = nullptr, *lane_upper = nullptr, *lane_x0 = nullptr;
   bool x_in_lane_layout = false, factor_in_lane_layout = false;
   // staging of solve()'s host arrays (allocated by the first solve())
   double *in_H = nullptr, *in_g = nullptr, *in_lower = nullptr, *in_upper = nullptr, *in_x0 = nullptr;
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
 };
 
 namespace
 {
-template<class T>
-int devAlloc(nmpc_hip_boxqp_solver * h, T ** p, size_t count)
-{
-  BQ_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
-  h->allocs.push_back(*p);
-  BQ_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
-  return NMPC_HIP_OK;
-}
-
 int validConfig(const nmpc_hip_boxqp_config & c)
 {
   if(c.max_iter < 1)
@@ -146,7 +106,7 @@ int launchSolve(nmpc_hip_boxqp_solver * h, const double * dH, const double * dg,
   const size_t B = h->B;
   const int n = h->n;
   const Kernel k = chosen(h);
-  BQ_TRY(hipEventRecord(h->ev0, s));
+  NMPC_CAPI_CHECK(h->beginLaunch(s));
   if(k == kLane)
   {
     const unsigned block = 256;
@@ -162,11 +122,9 @@ int launchSolve(nmpc_hip_boxqp_solver * h, const double * dH, const double * dg,
     const bq::WaveBuffers wb{dH, dg, dlo, dup, dx0, h->d_x, h->d_factor};
     hipLaunchKernelGGL(bq::boxqp_wave_kernel, dim3(static_cast<unsigned>(B)), dim3(64), bq::waveLdsBytes(n), s, wb, h->res, params(h), n);
   }
-  BQ_TRY(hipGetLastError());
-  BQ_TRY(hipEventRecord(h->ev1, s));
+  NMPC_CAPI_TRY(hipGetLastError());
+  NMPC_CAPI_CHECK(h->endLaunch(s));
   h->last = k;
-  h->last_stream = s;
-  h->timed = true;
   h->x_in_lane_layout = h->factor_in_lane_layout = (k == kLane);
   return NMPC_HIP_OK;
 }
@@ -200,6 +158,55 @@ int fieldBytes(const nmpc_hip_boxqp_solver * h, int field, size_t * bytes)
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[BoxQP] unknown field");
   }
 }
+
+bool solved(const nmpc_hip_boxqp_solver * h, int)
+{
+  return h->last != kAuto;
+}
+
+/** X and FACTOR of a lane-kernel solve: the transposing store into the boundary layout, once, on the stream of that solve. */
+int toBoundaryLayout(nmpc_hip_boxqp_solver * h, int field)
+{
+  const size_t B = h->B, n = h->n;
+  if(field == NMPC_HIP_BOXQP_FIELD_X && h->x_in_lane_layout)
+  {
+    hipLaunchKernelGGL(bq::boxqp_egress_kernel, dim3(blocksFor(B * n, 256)), dim3(256), 0, h->last_stream, h->lane.x, h->d_x, B,
+                       static_cast<int>(n));
+    NMPC_CAPI_TRY(hipGetLastError());
+    h->x_in_lane_layout = false;
+  }
+  if(field == NMPC_HIP_BOXQP_FIELD_FACTOR && h->factor_in_lane_layout)
+  {
+    hipLaunchKernelGGL(bq::boxqp_egress_kernel, dim3(blocksFor(B * n * n, 256)), dim3(256), 0, h->last_stream, h->lane.factor_out, h->d_factor,
+                       B, static_cast<int>(n * n));
+    NMPC_CAPI_TRY(hipGetLastError());
+    h->factor_in_lane_layout = false;
+  }
+  return NMPC_HIP_OK;
+}
+
+const void * fieldPtr(const nmpc_hip_boxqp_solver * h, int field)
+{
+  switch(field)
+  {
+    case NMPC_HIP_BOXQP_FIELD_X:
+      return h->d_x;
+    case NMPC_HIP_BOXQP_FIELD_FACTOR:
+      return h->d_factor;
+    case NMPC_HIP_BOXQP_FIELD_RETVAL:
+      return h->res.retval;
+    case NMPC_HIP_BOXQP_FIELD_ITER:
+      return h->res.iter;
+    case NMPC_HIP_BOXQP_FIELD_FACTORIZATION_NUM:
+      return h->res.factorization_num;
+    case NMPC_HIP_BOXQP_FIELD_FREE_MASK:
+      return h->res.free_mask;
+    case NMPC_HIP_BOXQP_FIELD_OBJ:
+      return h->res.obj;
+    default:
+      return h->d_trace;
+  }
+}
 } // namespace
 
 extern "C"
@@ -226,34 +233,10 @@ extern "C"
     {
       return NMPC_HIP_OK;
     }
-    (void)hipSetDevice(h->device);
-    if(h->last_stream)
-    {
-      (void)hipStreamSynchronize(h->last_stream);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamSynchronize(h->stream);
-    }
-    for(void * p : h->allocs)
-    {
-      (void)hipFree(p);
-    }
+    h->close(); // waits for the work that writes the trace
     if(h->d_trace)
     {
       (void)hipFree(h->d_trace);
-    }
-    if(h->ev0)
-    {
-      (void)hipEventDestroy(h->ev0);
-    }
-    if(h->ev1)
-    {
-      (void)hipEventDestroy(h->ev1);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamDestroy(h->stream);
     }
     delete h;
     return NMPC_HIP_OK;
@@ -274,64 +257,57 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[BoxQP] batch must be positive: " + std::to_string(batch));
     }
-    {
-      const int rc = checkDevice(device);
-      if(rc != NMPC_HIP_OK)
-      {
-        return rc;
-      }
-    }
+    NMPC_CAPI_CHECK(capi::checkDevice<Family>(device));
     auto * h = new nmpc_hip_boxqp_solver();
     h->n = var_dim;
     h->B = batch;
     h->device = device;
     nmpc_hip_boxqp_default_config(&h->cfg);
+    auto cleanup = [&](int code) {
+      nmpc_hip_boxqp_destroy(h);
+      return code;
+    };
+    int rc = h->open();
+    if(rc != NMPC_HIP_OK)
+    {
+      return cleanup(rc);
+    }
     const size_t B = batch, n = var_dim;
-    int rc = NMPC_HIP_OK;
-    auto A = [&](auto ** p, size_t count) {
+    auto A = [&](auto ** p, size_t count, const char * what) {
       if(rc == NMPC_HIP_OK)
       {
-        rc = devAlloc(h, p, count);
+        rc = h->devAlloc(p, count, what);
       }
     };
-    A(&h->d_x, B * n);
-    A(&h->d_factor, B * n * n);
-    A(&h->res.retval, B);
-    A(&h->res.iter, B);
-    A(&h->res.factorization_num, B);
-    A(&h->res.free_mask, B);
-    A(&h->res.obj, B);
+    A(&h->d_x, B * n, "x");
+    A(&h->d_factor, B * n * n, "the factor");
+    A(&h->res.retval, B, "retval");
+    A(&h->res.iter, B, "iter");
+    A(&h->res.factorization_num, B, "factorization_num");
+    A(&h->res.free_mask, B, "the free masks");
+    A(&h->res.obj, B, "obj");
     if(var_dim <= NMPC_HIP_BOXQP_LANE_MAX_DIM)
     {
-      A(&h->lane_H, B * n * n);
-      A(&h->lane_g, B * n);
-      A(&h->lane_lower, B * n);
-      A(&h->lane_upper, B * n);
-      A(&h->lane_x0, B * n);
-      A(&h->lane.x, B * n);
-      A(&h->lane.grad, B * n);
-      A(&h->lane.dir, B * n);
-      A(&h->lane.cand, B * n);
-      A(&h->lane.fac, B * n * n);
-      A(&h->lane.factor_out, B * n * n);
+      A(&h->lane_H, B * n * n, "the lane kernel's H");
+      A(&h->lane_g, B * n, "the lane kernel's g");
+      A(&h->lane_lower, B * n, "the lane kernel's lower");
+      A(&h->lane_upper, B * n, "the lane kernel's upper");
+      A(&h->lane_x0, B * n, "the lane kernel's initial_x");
+      A(&h->lane.x, B * n, "the lane kernel's x");
+      A(&h->lane.grad, B * n, "the lane kernel's gradient");
+      A(&h->lane.dir, B * n, "the lane kernel's search direction");
+      A(&h->lane.cand, B * n, "the lane kernel's candidate");
+      A(&h->lane.fac, B * n * n, "the lane kernel's factor workspace");
+      A(&h->lane.factor_out, B * n * n, "the lane kernel's factor");
       h->lane.H = h->lane_H;
       h->lane.g = h->lane_g;
       h->lane.lower = h->lane_lower;
       h->lane.upper = h->lane_upper;
       h->lane.x0 = h->lane_x0;
     }
-    auto cleanup = [&](int code) {
-      nmpc_hip_boxqp_destroy(h);
-      return code;
-    };
     if(rc != NMPC_HIP_OK)
     {
       return cleanup(rc);
-    }
-    if(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess
-       || hipEventCreate(&h->ev1) != hipSuccess)
-    {
-      return cleanup(fail(NMPC_HIP_ERR_HIP, "stream / event creation failed"));
     }
     // (the wave kernel's LDS passes 64 KB at n = 64: that has to be requested per kernel and device)
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bq::boxqp_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -350,19 +326,13 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    {
-      const int rc = validConfig(*cfg);
-      if(rc != NMPC_HIP_OK)
-      {
-        return rc;
-      }
-    }
+    NMPC_CAPI_CHECK(validConfig(*cfg));
     if(cfg->trace_capacity != h->cfg.trace_capacity)
     {
-      BQ_TRY(hipSetDevice(h->device));
+      NMPC_CAPI_TRY(hipSetDevice(h->device));
       if(h->last_stream)
       {
-        BQ_TRY(hipStreamSynchronize(h->last_stream));
+        NMPC_CAPI_TRY(hipStreamSynchronize(h->last_stream));
       }
       if(h->d_trace)
       {
@@ -374,8 +344,8 @@ extern "C"
       if(cfg->trace_capacity > 0)
       {
         const size_t bytes = h->B * cfg->trace_capacity * bq::kTraceColumns * sizeof(double);
-        BQ_TRY(hipMalloc(&h->d_trace, bytes));
-        BQ_TRY(hipMemset(h->d_trace, 0, bytes));
+        NMPC_CAPI_CHECK(h->allocBytes(&h->d_trace, bytes, "the trace"));
+        NMPC_CAPI_CHECK(h->clear(h->d_trace, bytes));
         h->res.trace = static_cast<double *>(h->d_trace);
       }
     }
@@ -400,8 +370,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    BQ_TRY(hipSetDevice(h->device));
-    return launchSolve(h, d_H, d_g, d_lower, d_upper, d_initial_x, stream ? static_cast<hipStream_t>(stream) : h->stream);
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    return launchSolve(h, d_H, d_g, d_lower, d_upper, d_initial_x, h->streamFor(stream));
   }
 
   int nmpc_hip_boxqp_solve(nmpc_hip_boxqp_handle h, const double * H, const double * g, const double * lower, const double * upper,
@@ -411,17 +381,26 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    BQ_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const size_t B = h->B, n = h->n;
     if(!h->in_H)
     {
+      const struct
+      {
+        double ** p;
+        size_t count;
+        const char * what;
+      } stage[] = {{&h->in_H, B * n * n, "the staging copy of H"},
+                   {&h->in_g, B * n, "the staging copy of g"},
+                   {&h->in_lower, B * n, "the staging copy of lower"},
+                   {&h->in_upper, B * n, "the staging copy of upper"},
+                   {&h->in_x0, B * n, "the staging copy of initial_x"}};
       int rc = NMPC_HIP_OK;
-      for(auto pc : {std::make_pair(&h->in_H, B * n * n), std::make_pair(&h->in_g, B * n), std::make_pair(&h->in_lower, B * n),
-                     std::make_pair(&h->in_upper, B * n), std::make_pair(&h->in_x0, B * n)})
+      for(const auto & a : stage)
       {
         if(rc == NMPC_HIP_OK)
         {
-          rc = devAlloc(h, pc.first, pc.second);
+          rc = h->devAlloc(a.p, a.count, a.what);
         }
       }
       if(rc != NMPC_HIP_OK)
@@ -430,25 +409,17 @@ extern "C"
         return rc;
       }
     }
-    if(h->last_stream && h->last_stream != h->stream)
-    {
-      BQ_TRY(hipStreamSynchronize(h->last_stream)); // a solve_device on another stream may still be writing the results
-    }
-    BQ_TRY(hipMemcpyAsync(h->in_H, H, B * n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    BQ_TRY(hipMemcpyAsync(h->in_g, g, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    BQ_TRY(hipMemcpyAsync(h->in_lower, lower, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    BQ_TRY(hipMemcpyAsync(h->in_upper, upper, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_CHECK(h->waitForOtherStream()); // a solve_device on another stream may still be writing the results
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->in_H, H, B * n * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->in_g, g, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->in_lower, lower, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->in_upper, upper, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if(initial_x)
     {
-      BQ_TRY(hipMemcpyAsync(h->in_x0, initial_x, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(h->in_x0, initial_x, B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    const int rc = launchSolve(h, h->in_H, h->in_g, h->in_lower, h->in_upper, initial_x ? h->in_x0 : nullptr, h->stream);
-    if(rc != NMPC_HIP_OK)
-    {
-      return rc;
-    }
-    BQ_TRY(hipStreamSynchronize(h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(launchSolve(h, h->in_H, h->in_g, h->in_lower, h->in_upper, initial_x ? h->in_x0 : nullptr, h->stream));
+    return h->syncLast();
   }
 
   int nmpc_hip_boxqp_synchronize(nmpc_hip_boxqp_handle h)
@@ -457,9 +428,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    BQ_TRY(hipSetDevice(h->device));
-    BQ_TRY(hipStreamSynchronize(h->last_stream ? h->last_stream : h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    return h->syncLast();
   }
 
   int nmpc_hip_boxqp_field_bytes(nmpc_hip_boxqp_handle h, int field, size_t * bytes)
@@ -473,77 +443,10 @@ extern "C"
 
   int nmpc_hip_boxqp_get(nmpc_hip_boxqp_handle h, int field, void * out, size_t bytes, int on_device)
   {
-    if(!h)
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
-    }
     size_t want = 0;
-    {
-      const int rc = fieldBytes(h, field, &want);
-      if(rc != NMPC_HIP_OK)
-      {
-        return rc;
-      }
-    }
-    if(bytes != want || (!out && want > 0))
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[BoxQP] get: bytes must equal nmpc_hip_boxqp_field_bytes");
-    }
-    if(h->last == kAuto)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[BoxQP] get needs a solve first");
-    }
-    if(want == 0)
-    {
-      return NMPC_HIP_OK;
-    }
-    BQ_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->last_stream;
-    const size_t B = h->B, n = h->n;
-    const void * src = nullptr;
-    switch(field)
-    {
-      case NMPC_HIP_BOXQP_FIELD_X:
-        if(h->x_in_lane_layout) // the transposing store
-        {
-          hipLaunchKernelGGL(bq::boxqp_egress_kernel, dim3(blocksFor(B * n, 256)), dim3(256), 0, s, h->lane.x, h->d_x, B, static_cast<int>(n));
-          BQ_TRY(hipGetLastError());
-          h->x_in_lane_layout = false;
-        }
-        src = h->d_x;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_FACTOR:
-        if(h->factor_in_lane_layout)
-        {
-          hipLaunchKernelGGL(bq::boxqp_egress_kernel, dim3(blocksFor(B * n * n, 256)), dim3(256), 0, s, h->lane.factor_out, h->d_factor, B,
-                             static_cast<int>(n * n));
-          BQ_TRY(hipGetLastError());
-          h->factor_in_lane_layout = false;
-        }
-        src = h->d_factor;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_RETVAL:
-        src = h->res.retval;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_ITER:
-        src = h->res.iter;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_FACTORIZATION_NUM:
-        src = h->res.factorization_num;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_FREE_MASK:
-        src = h->res.free_mask;
-        break;
-      case NMPC_HIP_BOXQP_FIELD_OBJ:
-        src = h->res.obj;
-        break;
-      default:
-        src = h->d_trace;
-        break;
-    }
-    BQ_TRY(hipMemcpyAsync(out, src, want, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    BQ_TRY(hipStreamSynchronize(s));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(capi::beginGet<Family>(h, field, out, bytes, &want, fieldBytes, solved, "get needs a solve"));
+    NMPC_CAPI_CHECK(toBoundaryLayout(h, field));
+    return h->copyOut(out, fieldPtr(h, field), want, on_device, capi::kWaitAlways);
   }
 
   int nmpc_hip_boxqp_kernel_name(nmpc_hip_boxqp_handle h, const char ** name)
@@ -590,18 +493,11 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    if(!h->timed)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[BoxQP] last_solve_ms needs a solve first");
-    }
-    BQ_TRY(hipSetDevice(h->device));
-    BQ_TRY(hipEventSynchronize(h->ev1));
-    BQ_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return NMPC_HIP_OK;
+    return h->lastMs(ms, "last_solve_ms needs a solve");
   }
 
   const char * nmpc_hip_boxqp_last_error(void)
   {
-    return g_boxqp_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 }

@@ -13,10 +13,12 @@
 
 #include <unistd.h>
 
+#include <nmpc_amd/hip/capi_core.hpp>
 #include <nmpc_amd/hip/model_ops.hpp>
 #include <nmpc_amd/hip/ragged_schedule.hpp>
 #include <nmpc_amd/hip/stream_schedule.hpp>
 
+namespace capi = nmpc_amd::hip::capi;
 using nmpc_amd::hip::DeviceBuffers;
 using nmpc_amd::hip::KernelPlan;
 using nmpc_amd::hip::ModelOps;
@@ -31,23 +33,10 @@ namespace
 // nmpc_hip_ddp_request_hw_queues() only reports whether the runtime has (or will have) at least the queues asked for.
 constexpr int kRuntimeDefaultHwQueues = 4;
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family // (nmpc_hip_ddp_create words its device check itself: no noun)
 {
-  g_last_error = msg;
-  return code;
-}
-
-#define NMPC_HIP_TRY(expr)                                                                                     \
-  do                                                                                                           \
-  {                                                                                                            \
-    hipError_t e_ = (expr);                                                                                    \
-    if(e_ != hipSuccess)                                                                                       \
-    {                                                                                                          \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-    }                                                                                                          \
-  } while(0)
+};
+constexpr auto fail = capi::fail<Family>;
 
 std::vector<const ModelOps *> & registry()
 {
@@ -166,16 +155,16 @@ KernelPlan planOf(const nmpc_hip_ddp_solver * s)
 template<class T>
 int devAlloc(T ** p, size_t count)
 {
-  NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
-  NMPC_HIP_TRY(hipMemset(*p, 0, count * sizeof(T)));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
+  NMPC_CAPI_TRY(hipMemset(*p, 0, count * sizeof(T)));
   return NMPC_HIP_OK;
 }
 
 /** A Scalar array of `count` elements of `elem` bytes behind a double pointer. */
 int devAllocScalar(double ** p, size_t count, int elem)
 {
-  NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), count * static_cast<size_t>(elem)));
-  NMPC_HIP_TRY(hipMemset(*p, 0, count * static_cast<size_t>(elem)));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(p), count * static_cast<size_t>(elem)));
+  NMPC_CAPI_TRY(hipMemset(*p, 0, count * static_cast<size_t>(elem)));
   return NMPC_HIP_OK;
 }
 
@@ -187,11 +176,11 @@ int ensureStage(void ** p, size_t * have, size_t need)
   }
   if(*p)
   {
-    NMPC_HIP_TRY(hipFree(*p));
+    NMPC_CAPI_TRY(hipFree(*p));
     *p = nullptr;
     *have = 0;
   }
-  NMPC_HIP_TRY(hipMalloc(p, need));
+  NMPC_CAPI_TRY(hipMalloc(p, need));
   *have = need;
   return NMPC_HIP_OK;
 }
@@ -205,8 +194,8 @@ int allocTrace(nmpc_hip_ddp_solver * s)
   }
   if(s->d_trace)
   {
-    NMPC_HIP_TRY(hipDeviceSynchronize()); // a solve in flight may still write the old trace buffer
-    NMPC_HIP_TRY(hipFree(s->d_trace));
+    NMPC_CAPI_TRY(hipDeviceSynchronize()); // a solve in flight may still write the old trace buffer
+    NMPC_CAPI_TRY(hipFree(s->d_trace));
     s->d_trace = nullptr;
   }
   s->trace_rows = rows;
@@ -360,13 +349,13 @@ int packField(nmpc_hip_ddp_solver * s, int field, void * d_out, hipStream_t st)
   switch(field)
   {
     case NMPC_HIP_FIELD_X:
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_X, dout, s->d_sel, R, 2, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_X, dout, s->d_sel, R, 2, st));
       break;
     case NMPC_HIP_FIELD_U:
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_U, dout, s->d_sel, R, 2, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_U, dout, s->d_sel, R, 2, st));
       break;
     case NMPC_HIP_FIELD_COST:
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_cost, dout, s->d_sel, R, 2, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_cost, dout, s->d_sel, R, 2, st));
       break;
     case NMPC_HIP_FIELD_KFF:
     case NMPC_HIP_FIELD_KFB:
@@ -387,11 +376,11 @@ int packField(nmpc_hip_ddp_solver * s, int field, void * d_out, hipStream_t st)
           hipLaunchKernelGGL((nmpc_amd::hip::gain_records_to_batch_major_kernel<double>), grid, blk, 0, st,
                              reinterpret_cast<const double *>(s->d_wpi_ws), dout, total, s->MM + s->MM * s->N, per_step, offset);
         }
-        NMPC_HIP_TRY(hipGetLastError());
+        NMPC_CAPI_TRY(hipGetLastError());
       }
       else
       {
-        NMPC_HIP_TRY(scalarToMajor(s, field == NMPC_HIP_FIELD_KFF ? s->d_kff : s->d_Kfb, dout, nullptr, R, 1, st));
+        NMPC_CAPI_TRY(scalarToMajor(s, field == NMPC_HIP_FIELD_KFF ? s->d_kff : s->d_Kfb, dout, nullptr, R, 1, st));
       }
       break;
     case NMPC_HIP_FIELD_TRACE:
@@ -400,28 +389,28 @@ int packField(nmpc_hip_ddp_solver * s, int field, void * d_out, hipStream_t st)
         return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "full trace was not recorded: set trace_level = 1 before solve");
       }
       // rows beyond the last iteration of this solve are reported as zero (a reused handle keeps older rows on the device)
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_trace, dout, nullptr, R, 1, st, s->d_iters, NMPC_HIP_NTRACE));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_trace, dout, nullptr, R, 1, st, s->d_iters, NMPC_HIP_NTRACE));
       break;
     case NMPC_HIP_FIELD_TRACE_LAST:
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_trace_last, dout, nullptr, R, 1, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_trace_last, dout, nullptr, R, 1, st));
       break;
     case NMPC_HIP_FIELD_DV:
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_dV, dout, nullptr, R, 1, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_dV, dout, nullptr, R, 1, st));
       break;
     case NMPC_HIP_FIELD_STATUS:
-      NMPC_HIP_TRY(hipMemcpyAsync(iout, s->d_status, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+      NMPC_CAPI_TRY(hipMemcpyAsync(iout, s->d_status, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
       break;
     case NMPC_HIP_FIELD_ITERS:
-      NMPC_HIP_TRY(hipMemcpyAsync(iout, s->d_iters, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+      NMPC_CAPI_TRY(hipMemcpyAsync(iout, s->d_iters, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
       break;
     case NMPC_HIP_FIELD_QP_RETVAL:
-      NMPC_HIP_TRY(toMajor<int>(s->d_qp_ret, iout, nullptr, B, R, Bp, 1, st));
+      NMPC_CAPI_TRY(toMajor<int>(s->d_qp_ret, iout, nullptr, B, R, Bp, 1, st));
       break;
     case NMPC_HIP_FIELD_INPUT_DIM:
-      NMPC_HIP_TRY(toMajor<int>(s->d_input_dim, iout, nullptr, B, R, Bp, 1, st));
+      NMPC_CAPI_TRY(toMajor<int>(s->d_input_dim, iout, nullptr, B, R, Bp, 1, st));
       break;
     case NMPC_HIP_FIELD_QP_FREE_MASK:
-      NMPC_HIP_TRY(toMajor<unsigned>(s->d_qp_free, static_cast<unsigned *>(d_out), nullptr, B, R, Bp, 1, st));
+      NMPC_CAPI_TRY(toMajor<unsigned>(s->d_qp_free, static_cast<unsigned *>(d_out), nullptr, B, R, Bp, 1, st));
       break;
     default:
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "unknown field");
@@ -436,16 +425,16 @@ int harvestSlot(nmpc_hip_ddp_solver * s, int slot)
   {
     return NMPC_HIP_OK;
   }
-  NMPC_HIP_TRY(hipEventSynchronize(s->ev_end[slot]));
+  NMPC_CAPI_TRY(hipEventSynchronize(s->ev_end[slot]));
   float tot = 0, ker = 0;
-  NMPC_HIP_TRY(hipEventElapsedTime(&tot, s->ev_begin[slot], s->ev_end[slot]));
+  NMPC_CAPI_TRY(hipEventElapsedTime(&tot, s->ev_begin[slot], s->ev_end[slot]));
   if(s->ev_fused[slot])
   {
     ker = tot; // the conversion is part of the solve kernel: begin -> end
   }
   else
   {
-    NMPC_HIP_TRY(hipEventElapsedTime(&ker, s->ev_kernel[slot], s->ev_end[slot]));
+    NMPC_CAPI_TRY(hipEventElapsedTime(&ker, s->ev_kernel[slot], s->ev_end[slot]));
   }
   s->sum_total_ms += tot;
   s->sum_kernel_ms += ker;
@@ -586,7 +575,7 @@ int ensureRagged(nmpc_hip_ddp_solver * s)
   }
   // devAlloc clears with hipMemset, which is ordered on the NULL stream; the handle's stream is non-blocking and the first
   // launches of the schedule follow at once: without this wait the clear could land in the middle of them (once per handle)
-  NMPC_HIP_TRY(hipDeviceSynchronize());
+  NMPC_CAPI_TRY(hipDeviceSynchronize());
   s->ragged_ready = true;
   return NMPC_HIP_OK;
 }
@@ -697,7 +686,7 @@ int launchRagged(nmpc_hip_ddp_solver * s, hipStream_t st, DeviceBuffers buf, con
     (void)hipGetLastError();
     return fail(NMPC_HIP_ERR_HIP, std::string("resumable launch: ") + hipGetErrorString(le));
   }
-  NMPC_HIP_TRY(hipGetLastError());
+  NMPC_CAPI_TRY(hipGetLastError());
   s->last_ragged_rounds = rounds;
   return NMPC_HIP_OK;
 }
@@ -725,7 +714,7 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
     {
       return rc;
     }
-    NMPC_HIP_TRY(hipDeviceSynchronize()); // (devAlloc's clears are ordered on the NULL stream)
+    NMPC_CAPI_TRY(hipDeviceSynchronize()); // (devAlloc's clears are ordered on the NULL stream)
   }
   int * w = s->d_stream_words;
   DeviceBuffers buf = makeBuffers(s);
@@ -753,12 +742,12 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
       }
     }
   } tev;
-  NMPC_HIP_TRY(hipEventCreate(&tev.a));
-  NMPC_HIP_TRY(hipEventCreate(&tev.b));
+  NMPC_CAPI_TRY(hipEventCreate(&tev.a));
+  NMPC_CAPI_TRY(hipEventCreate(&tev.b));
   hipEvent_t ev0 = tev.a, ev1 = tev.b;
-  NMPC_HIP_TRY(hipEventRecord(ev0, st));
+  NMPC_CAPI_TRY(hipEventRecord(ev0, st));
   hipLaunchKernelGGL(stream_begin_kernel, dim3(1), dim3(64), 0, st, w, n_total);
-  NMPC_HIP_TRY(hipMemsetAsync(s->d_stream_id, 0xff, static_cast<size_t>(s->Bp) * sizeof(int), st)); // every slot empty (-1)
+  NMPC_CAPI_TRY(hipMemsetAsync(s->d_stream_id, 0xff, static_cast<size_t>(s->Bp) * sizeof(int), st)); // every slot empty (-1)
   if(own)
   {
     // every one of the Bp rows starts with the shared problem object and limits (the words say "nothing filled yet"): the lanes of
@@ -803,13 +792,13 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
       }
     }
   } host;
-  NMPC_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&host.done), kAhead * sizeof(int), hipHostMallocDefault));
+  NMPC_CAPI_TRY(hipHostMalloc(reinterpret_cast<void **>(&host.done), kAhead * sizeof(int), hipHostMallocDefault));
   int * h_done = host.done;
   hipEvent_t * ev_blk = host.ev;
   for(int k = 0; k < kAhead; k++)
   {
     h_done[k] = 0;
-    NMPC_HIP_TRY(hipEventCreateWithFlags(&ev_blk[k], hipEventDisableTiming));
+    NMPC_CAPI_TRY(hipEventCreateWithFlags(&ev_blk[k], hipEventDisableTiming));
   }
   long long queued_blocks = 0;
   while(le == hipSuccess && done < n_total && rounds < max_rounds)
@@ -817,7 +806,7 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
     const int slot = static_cast<int>(queued_blocks % kAhead);
     if(queued_blocks >= kAhead)
     {
-      NMPC_HIP_TRY(hipEventSynchronize(ev_blk[slot])); // the block queued kAhead blocks ago
+      NMPC_CAPI_TRY(hipEventSynchronize(ev_blk[slot])); // the block queued kAhead blocks ago
       done = h_done[slot];
       if(done >= n_total)
       {
@@ -841,13 +830,13 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
     {
       break;
     }
-    NMPC_HIP_TRY(hipMemcpyAsync(&h_done[slot], w + kSwDone, sizeof(int), hipMemcpyDeviceToHost, st));
-    NMPC_HIP_TRY(hipEventRecord(ev_blk[slot], st));
+    NMPC_CAPI_TRY(hipMemcpyAsync(&h_done[slot], w + kSwDone, sizeof(int), hipMemcpyDeviceToHost, st));
+    NMPC_CAPI_TRY(hipEventRecord(ev_blk[slot], st));
     queued_blocks++;
   }
   if(le == hipSuccess)
   {
-    NMPC_HIP_TRY(hipStreamSynchronize(st));
+    NMPC_CAPI_TRY(hipStreamSynchronize(st));
     for(int k = 0; k < kAhead; k++)
     {
       done = h_done[k] > done ? h_done[k] : done;
@@ -858,10 +847,10 @@ int launchStream(nmpc_hip_ddp_solver * s, hipStream_t st, const KernelPlan & pla
     (void)hipGetLastError();
     return fail(NMPC_HIP_ERR_HIP, std::string("streamed solve: ") + hipGetErrorString(le));
   }
-  NMPC_HIP_TRY(hipGetLastError());
-  NMPC_HIP_TRY(hipEventRecord(ev1, st));
-  NMPC_HIP_TRY(hipEventSynchronize(ev1));
-  NMPC_HIP_TRY(hipEventElapsedTime(&s->stream_ms, ev0, ev1));
+  NMPC_CAPI_TRY(hipGetLastError());
+  NMPC_CAPI_TRY(hipEventRecord(ev1, st));
+  NMPC_CAPI_TRY(hipEventSynchronize(ev1));
+  NMPC_CAPI_TRY(hipEventElapsedTime(&s->stream_ms, ev0, ev1));
   s->stream_rounds = rounds;
   if(done < n_total)
   {
@@ -897,7 +886,7 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
     {
       return hrc;
     }
-    NMPC_HIP_TRY(hipEventRecord(s->ev_begin[slot], st));
+    NMPC_CAPI_TRY(hipEventRecord(s->ev_begin[slot], st));
   }
   std::vector<int> caps;
   bool whole_solve = !raggedRounds(s, plan, &caps);
@@ -917,14 +906,14 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
       hipLaunchKernelGGL((nmpc_amd::hip::ingest_kernel<double, double>), grid, dim3(256), 0, st, d_t0, s->d_t0, d_x0, s->d_x0, s->N,
                          d_u_init, s->d_U, RU, s->B);
     }
-    NMPC_HIP_TRY(hipGetLastError());
+    NMPC_CAPI_TRY(hipGetLastError());
   }
   if(timed)
   {
     s->ev_fused[slot] = fused;
     if(!fused)
     {
-      NMPC_HIP_TRY(hipEventRecord(s->ev_kernel[slot], st));
+      NMPC_CAPI_TRY(hipEventRecord(s->ev_kernel[slot], st));
     }
   }
   DeviceBuffers buf = makeBuffers(s);
@@ -955,11 +944,11 @@ int launchRecorded(nmpc_hip_ddp_solver * s,
                                           "only; this solve needs the single-wavefront kernel"
                                         : std::string(plan.kernelName()) + " has no instantiation for this solve");
     }
-    NMPC_HIP_TRY(le);
+    NMPC_CAPI_TRY(le);
   }
   if(timed)
   {
-    NMPC_HIP_TRY(hipEventRecord(s->ev_end[slot], st));
+    NMPC_CAPI_TRY(hipEventRecord(s->ev_end[slot], st));
     s->ev_pending[slot] = true;
     s->n_solves++;
   }
@@ -986,7 +975,7 @@ extern "C"
 
   const char * nmpc_hip_ddp_last_error(void)
   {
-    return g_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 
   int nmpc_hip_ddp_default_config(nmpc_hip_ddp_config * c)
@@ -1134,7 +1123,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
     }
-    NMPC_HIP_TRY(hipSetDevice(device));
+    NMPC_CAPI_TRY(hipSetDevice(device));
 
     nmpc_hip_ddp_solver * s = new nmpc_hip_ddp_solver();
     s->ops = m;
@@ -1220,14 +1209,14 @@ extern "C"
     }
     if(rc != NMPC_HIP_OK)
     {
-      std::string keep = g_last_error;
+      std::string keep = capi::lastError<Family>();
       nmpc_hip_ddp_destroy(s);
-      g_last_error = keep;
+      capi::lastError<Family>() = keep;
       return rc;
     }
     // devAlloc clears every buffer with hipMemset, which is ordered on the NULL stream; the handle's stream is non-blocking, and a
     // caller in compiled code launches its first solve microseconds from here: the clears must have landed (once per handle)
-    NMPC_HIP_TRY(hipDeviceSynchronize());
+    NMPC_CAPI_TRY(hipDeviceSynchronize());
     *out = s;
     return NMPC_HIP_OK;
   }
@@ -1309,7 +1298,7 @@ extern "C"
     {
       return rc;
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     s->cfg = *cfg; // kernels capture the configuration by value at launch, so no synchronisation is needed
     return allocTrace(s); // (re)allocates, after a device synchronise, only when the trace size changes
   }
@@ -1345,13 +1334,13 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle, or only one of lower / upper given");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
-    NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
     if(!lower)
     {
       if(s->d_lim_batch)
       {
-        NMPC_HIP_TRY(hipFree(s->d_lim_batch));
+        NMPC_CAPI_TRY(hipFree(s->d_lim_batch));
         s->d_lim_batch = nullptr;
       }
       s->has_limits = s->has_shared_limits || s->d_lim_steps != nullptr; // back to what nmpc_hip_ddp_set_input_limits gave, if anything
@@ -1370,9 +1359,9 @@ extern "C"
     }
     if(!s->d_lim_batch)
     {
-      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_batch), host.size() * sizeof(double)));
+      NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_batch), host.size() * sizeof(double)));
     }
-    NMPC_HIP_TRY(hipMemcpy(s->d_lim_batch, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMemcpy(s->d_lim_batch, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
     s->has_limits = true;
     return NMPC_HIP_OK;
   }
@@ -1383,13 +1372,13 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     if(!params)
     {
       if(s->d_params_batch)
       {
-        NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
-        NMPC_HIP_TRY(hipFree(s->d_params_batch));
+        NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
+        NMPC_CAPI_TRY(hipFree(s->d_params_batch));
         s->d_params_batch = nullptr;
       }
       return NMPC_HIP_OK;
@@ -1419,7 +1408,7 @@ extern "C"
     }
     if(!s->d_params_batch)
     {
-      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_params_batch), static_cast<size_t>(s->Bp) * pb));
+      NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_params_batch), static_cast<size_t>(s->Bp) * pb));
     }
     // padding lanes (b >= B) run on the shared object
     std::vector<unsigned char> host(static_cast<size_t>(s->Bp) * pb);
@@ -1428,8 +1417,8 @@ extern "C"
     {
       std::memcpy(host.data() + static_cast<size_t>(b) * pb, s->params.data(), pb);
     }
-    NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
-    NMPC_HIP_TRY(hipMemcpy(s->d_params_batch, host.data(), host.size(), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
+    NMPC_CAPI_TRY(hipMemcpy(s->d_params_batch, host.data(), host.size(), hipMemcpyHostToDevice));
     return NMPC_HIP_OK;
   }
 
@@ -1469,13 +1458,13 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "a limits table needs at least horizon_steps rows");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
-    NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
     if(!lower)
     {
       if(s->d_lim_steps)
       {
-        NMPC_HIP_TRY(hipFree(s->d_lim_steps));
+        NMPC_CAPI_TRY(hipFree(s->d_lim_steps));
         s->d_lim_steps = nullptr;
       }
       s->lim_steps_per_instance = 0;
@@ -1502,11 +1491,11 @@ extern "C"
     }
     if(s->d_lim_steps)
     {
-      NMPC_HIP_TRY(hipFree(s->d_lim_steps));
+      NMPC_CAPI_TRY(hipFree(s->d_lim_steps));
       s->d_lim_steps = nullptr;
     }
-    NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_steps), host.size() * sizeof(double)));
-    NMPC_HIP_TRY(hipMemcpy(s->d_lim_steps, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_steps), host.size() * sizeof(double)));
+    NMPC_CAPI_TRY(hipMemcpy(s->d_lim_steps, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
     s->lim_steps_per_instance = per_instance ? 1 : 0;
     s->lim_rows = rows;
     s->lim_offset = 0;
@@ -1534,7 +1523,7 @@ extern "C"
       return fail(NMPC_HIP_ERR_RUNTIME, "with_input_constraint is set but no input limits were given "
                                         "(setInputLimitsFunc, DDPSolver.h:282-285)");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
     return launchRecorded(s, st, d_t0, d_x0, d_u_init, true, true, true);
   }
@@ -1603,7 +1592,7 @@ extern "C"
       return fail(NMPC_HIP_ERR_RUNTIME, "with_input_constraint is set but no input limits were given "
                                         "(setInputLimitsFunc, DDPSolver.h:282-285)");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     hipStream_t st = s->stream;
     const size_t B = static_cast<size_t>(s->B), nt = static_cast<size_t>(opt->n_ticks);
     const size_t nx = B * s->N, nu = B * s->T * s->MM;
@@ -1625,11 +1614,11 @@ extern "C"
     double * dx = static_cast<double *>(s->d_stage_in);
     double * du = dx + nx;
     double * dt = du + nu;
-    NMPC_HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, st));
-    NMPC_HIP_TRY(hipMemcpyAsync(du, u_init, nu * sizeof(double), hipMemcpyHostToDevice, st));
+    NMPC_CAPI_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, st));
+    NMPC_CAPI_TRY(hipMemcpyAsync(du, u_init, nu * sizeof(double), hipMemcpyHostToDevice, st));
     if(t0)
     {
-      NMPC_HIP_TRY(hipMemcpyAsync(dt, t0, B * sizeof(double), hipMemcpyHostToDevice, st));
+      NMPC_CAPI_TRY(hipMemcpyAsync(dt, t0, B * sizeof(double), hipMemcpyHostToDevice, st));
     }
     nmpc_amd::hip::MpcAdvanceArgs args;
     args.n_ticks = opt->n_ticks;
@@ -1678,25 +1667,25 @@ extern "C"
     auto out = [&](void * host, const void * dev, size_t bytes) -> hipError_t {
       return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
     };
-    NMPC_HIP_TRY(out(t_log, args.t_log, B * nt * sizeof(double)));
-    NMPC_HIP_TRY(out(x_log, args.x_log, B * nt * s->N * sizeof(double)));
-    NMPC_HIP_TRY(out(u0_log, args.u0_log, B * nt * s->MM * sizeof(double)));
-    NMPC_HIP_TRY(out(iter_log, args.iter_log, B * nt * sizeof(int)));
-    NMPC_HIP_TRY(out(status_log, args.status_log, B * nt * sizeof(int)));
-    NMPC_HIP_TRY(out(m0_log, args.m0_log, B * nt * sizeof(int)));
+    NMPC_CAPI_TRY(out(t_log, args.t_log, B * nt * sizeof(double)));
+    NMPC_CAPI_TRY(out(x_log, args.x_log, B * nt * s->N * sizeof(double)));
+    NMPC_CAPI_TRY(out(u0_log, args.u0_log, B * nt * s->MM * sizeof(double)));
+    NMPC_CAPI_TRY(out(iter_log, args.iter_log, B * nt * sizeof(int)));
+    NMPC_CAPI_TRY(out(status_log, args.status_log, B * nt * sizeof(int)));
+    NMPC_CAPI_TRY(out(m0_log, args.m0_log, B * nt * sizeof(int)));
     // the logs have been queued for copy-out on the same stream: the input staging buffer can be reused behind them
     // (the handle's t0 / x0 are arrays of the problem's Scalar: converted on the way out)
     if(t_final)
     {
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_t0, dt, nullptr, 1, 1, st));
-      NMPC_HIP_TRY(hipMemcpyAsync(t_final, dt, B * sizeof(double), hipMemcpyDeviceToHost, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_t0, dt, nullptr, 1, 1, st));
+      NMPC_CAPI_TRY(hipMemcpyAsync(t_final, dt, B * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     if(x_final)
     {
-      NMPC_HIP_TRY(scalarToMajor(s, s->d_x0, dx, nullptr, s->N, 1, st));
-      NMPC_HIP_TRY(hipMemcpyAsync(x_final, dx, nx * sizeof(double), hipMemcpyDeviceToHost, st));
+      NMPC_CAPI_TRY(scalarToMajor(s, s->d_x0, dx, nullptr, s->N, 1, st));
+      NMPC_CAPI_TRY(hipMemcpyAsync(x_final, dx, nx * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    NMPC_HIP_TRY(hipStreamSynchronize(st));
+    NMPC_CAPI_TRY(hipStreamSynchronize(st));
     return NMPC_HIP_OK;
   }
 
@@ -1706,8 +1695,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
-    NMPC_HIP_TRY(hipStreamSynchronize(s->last_stream ? s->last_stream : s->stream));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->last_stream ? s->last_stream : s->stream));
     return NMPC_HIP_OK;
   }
 
@@ -1720,7 +1709,7 @@ extern "C"
     {
       return rc;
     }
-    NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
     return NMPC_HIP_OK;
   }
 
@@ -1735,7 +1724,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle, x0 or u_init");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     const size_t nx = static_cast<size_t>(s->B) * s->N;
     const size_t nu = static_cast<size_t>(s->B) * s->T * s->MM;
     const size_t nt = static_cast<size_t>(s->B);
@@ -1747,23 +1736,23 @@ extern "C"
     double * dx = static_cast<double *>(s->d_stage_in);
     double * du = dx + nx;
     double * dt = du + nu;
-    NMPC_HIP_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    NMPC_HIP_TRY(hipMemcpyAsync(du, u_init, nu * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(du, u_init, nu * sizeof(double), hipMemcpyHostToDevice, s->stream));
     if(t0)
     {
-      NMPC_HIP_TRY(hipMemcpyAsync(dt, t0, nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(dt, t0, nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
     }
     // The host arrays may be reused when this call returns: wait for the staging copies (pageable memory: the runtime may pin the
     // caller's pages and copy later) — for them only, the solve behind them stays queued.
     if(!s->ev_staged)
     {
-      NMPC_HIP_TRY(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
+      NMPC_CAPI_TRY(hipEventCreateWithFlags(&s->ev_staged, hipEventDisableTiming));
     }
-    NMPC_HIP_TRY(hipEventRecord(s->ev_staged, s->stream));
+    NMPC_CAPI_TRY(hipEventRecord(s->ev_staged, s->stream));
     s->queued_solve = queued;
     rc = nmpc_hip_ddp_solve_device(s, t0 ? dt : nullptr, dx, du, nullptr);
     s->queued_solve = false;
-    NMPC_HIP_TRY(hipEventSynchronize(s->ev_staged));
+    NMPC_CAPI_TRY(hipEventSynchronize(s->ev_staged));
     return rc;
   }
 
@@ -1855,8 +1844,8 @@ extern "C"
     {
       span = 8; // [measured, profiles/r06_stream_throughput.txt: 4 / 6 / 8 / 12 / 16 iterations per round: 10.3 / 10.8 / 10.9 / 10.5 / 10.1 k]
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
-    NMPC_HIP_TRY(hipStreamSynchronize(s->stream));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(s->stream));
     constexpr size_t kLim = 2 * nmpc_amd::hip::kMaxInputDim; // doubles of one limits row
     const size_t N = static_cast<size_t>(n_instances), T = static_cast<size_t>(s->T), n = static_cast<size_t>(s->N), mm = static_cast<size_t>(s->MM);
     const size_t n_t0 = N, n_x0 = N * n, n_u = N * T * mm, n_X = N * (T + 1) * n, n_c = N * (T + 1), n_tr = N * NMPC_HIP_NTRACE, n_dv = N * 2;
@@ -1868,11 +1857,11 @@ extern "C"
     {
       if(s->d_stream_io)
       {
-        NMPC_HIP_TRY(hipFree(s->d_stream_io));
+        NMPC_CAPI_TRY(hipFree(s->d_stream_io));
         s->d_stream_io = nullptr;
         s->stream_io_bytes = 0;
       }
-      NMPC_HIP_TRY(hipMalloc(&s->d_stream_io, bytes));
+      NMPC_CAPI_TRY(hipMalloc(&s->d_stream_io, bytes));
       s->stream_io_bytes = bytes;
     }
     s->stream_n = 0;
@@ -1895,10 +1884,10 @@ extern "C"
     unsigned char * d_params_queue = reinterpret_cast<unsigned char *>(io.iters + N); // (8-byte aligned: 2 N ints behind doubles)
     if(t0)
     {
-      NMPC_HIP_TRY(hipMemcpyAsync(d_t0, t0, n_t0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(d_t0, t0, n_t0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
     }
-    NMPC_HIP_TRY(hipMemcpyAsync(d_x0, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    NMPC_HIP_TRY(hipMemcpyAsync(d_u, u_init, n_u * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(d_x0, x0, n_x0 * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(d_u, u_init, n_u * sizeof(double), hipMemcpyHostToDevice, s->stream));
     if(!own_params && !own_limits)
     {
       int rc = launchStream(s, s->stream, plan, io, n_instances, span);
@@ -1938,9 +1927,9 @@ extern "C"
     nmpc_amd::hip::StreamOwn own = {};
     if(own_params)
     {
-      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_params_batch), static_cast<size_t>(s->Bp) * pb));
-      NMPC_HIP_TRY(hipMemcpyAsync(d_params_queue, in->params, N * pb, hipMemcpyHostToDevice, s->stream));
-      NMPC_HIP_TRY(hipMemcpyAsync(d_params_queue + N * pb, s->params.data(), pb, hipMemcpyHostToDevice, s->stream));
+      NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_params_batch), static_cast<size_t>(s->Bp) * pb));
+      NMPC_CAPI_TRY(hipMemcpyAsync(d_params_queue, in->params, N * pb, hipMemcpyHostToDevice, s->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(d_params_queue + N * pb, s->params.data(), pb, hipMemcpyHostToDevice, s->stream));
       own.params_slots = reinterpret_cast<unsigned *>(s->d_params_batch);
       own.params_queue = reinterpret_cast<const unsigned *>(d_params_queue);
       own.params_shared = reinterpret_cast<const unsigned *>(d_params_queue + N * pb);
@@ -1959,8 +1948,8 @@ extern "C"
           h_lim[(q * 2 + 1) * kMax + a] = given ? in->upper[q * mm + a] : (q < N ? INFINITY : s->lim_hi[a]);
         }
       }
-      NMPC_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_batch), static_cast<size_t>(s->Bp) * kLim * sizeof(double)));
-      NMPC_HIP_TRY(hipMemcpyAsync(d_lim_queue, h_lim.data(), n_lim * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_lim_batch), static_cast<size_t>(s->Bp) * kLim * sizeof(double)));
+      NMPC_CAPI_TRY(hipMemcpyAsync(d_lim_queue, h_lim.data(), n_lim * sizeof(double), hipMemcpyHostToDevice, s->stream));
       own.lim_slots = s->d_lim_batch;
       own.lim_queue = d_lim_queue;
       own.lim_shared = d_lim_queue + N * kLim;
@@ -2005,8 +1994,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "output size: " + std::to_string(want) + " bytes expected");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
-    NMPC_HIP_TRY(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
     return NMPC_HIP_OK;
   }
 
@@ -2064,7 +2053,7 @@ extern "C"
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT,
                   "field size should be " + std::to_string(need) + " but " + std::to_string(bytes) + ".");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : (s->last_stream ? s->last_stream : s->stream);
     return packField(s, field, d_out, st);
   }
@@ -2090,7 +2079,7 @@ extern "C"
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT,
                   "field size should be " + std::to_string(need) + " but " + std::to_string(bytes) + ".");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     hipStream_t st = s->last_stream ? s->last_stream : s->stream;
     rc = ensureStage(&s->d_stage_out, &s->stage_out_bytes, need);
     if(rc != NMPC_HIP_OK)
@@ -2102,8 +2091,8 @@ extern "C"
     {
       return rc;
     }
-    NMPC_HIP_TRY(hipMemcpyAsync(out, s->d_stage_out, need, hipMemcpyDeviceToHost, st));
-    NMPC_HIP_TRY(hipStreamSynchronize(st));
+    NMPC_CAPI_TRY(hipMemcpyAsync(out, s->d_stage_out, need, hipMemcpyDeviceToHost, st));
+    NMPC_CAPI_TRY(hipStreamSynchronize(st));
     return NMPC_HIP_OK;
   }
 
@@ -2117,7 +2106,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "solve() has not been called");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     int rc = harvestAll(s);
     if(rc != NMPC_HIP_OK)
     {
@@ -2144,14 +2133,14 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "solve() has not been called");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     int rc = harvestAll(s); // (waits for the last solve)
     if(rc != NMPC_HIP_OK)
     {
       return rc;
     }
     std::vector<unsigned long long> host(static_cast<size_t>(s->B) * 4);
-    NMPC_HIP_TRY(hipMemcpy(host.data(), s->d_phase_ticks, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    NMPC_CAPI_TRY(hipMemcpy(host.data(), s->d_phase_ticks, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     // The waves that drive the instances run side by side for the whole launch: the split of the kernel's time is the split of
     // the longest-running wave's ticks (the one that sets the kernel's duration).
     size_t worst = 0;
@@ -2251,7 +2240,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    NMPC_HIP_TRY(hipSetDevice(s->device));
+    NMPC_CAPI_TRY(hipSetDevice(s->device));
     int rc = harvestAll(s);
     if(rc != NMPC_HIP_OK)
     {

@@ -10,9 +10,11 @@
 #include <vector>
 
 #define NMPC_AMD_CGMRES_COMMON_KERNELS // cgmres_gmres_dense_kernel lives in this translation unit
+#include <nmpc_amd/hip/capi_core.hpp>
 #include <nmpc_amd/hip/cgmres_kernels.hpp>
 #include <nmpc_amd/hip/cgmres_wave_kernels.hpp> // CgmresWaveOps and waveLdsBytes; the wave kernels live in cgmres_wave_models.hip
 
+namespace capi = nmpc_amd::hip::capi;
 namespace cg = nmpc_amd::hip::cgmres;
 using cg::CgmresBuffers;
 using cg::CgmresOps;
@@ -20,23 +22,11 @@ using cg::CgmresWaveOps;
 
 namespace
 {
-thread_local std::string g_cgmres_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family
 {
-  g_cgmres_last_error = msg;
-  return code;
-}
-
-#define CG_TRY(expr)                                                                      \
-  do                                                                                      \
-  {                                                                                       \
-    hipError_t e_ = (expr);                                                               \
-    if(e_ != hipSuccess)                                                                  \
-    {                                                                                     \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    }                                                                                     \
-  } while(0)
+  static constexpr const char * noun = "the C/GMRES solver";
+};
+constexpr auto fail = capi::fail<Family>;
 
 std::vector<const CgmresOps *> & registry()
 {
@@ -116,23 +106,6 @@ __global__ void cgmres_fill_kernel(double * p, size_t n, double v)
   }
 }
 
-int checkDevice(int device)
-{
-  int n_dev = 0;
-  const hipError_t e = hipGetDeviceCount(&n_dev);
-  if(e != hipSuccess || n_dev <= 0)
-  {
-    return fail(NMPC_HIP_ERR_NO_DEVICE, std::string("no HIP device available (") + hipGetErrorString(e) +
-                                            "): the C/GMRES solver has no CPU fallback");
-  }
-  if(device < 0 || device >= n_dev)
-  {
-    return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
-  }
-  CG_TRY(hipSetDevice(device));
-  return NMPC_HIP_OK;
-}
-
 /** RAII device buffer for the one-shot diagnostics. */
 struct DevBuf
 {
@@ -173,9 +146,9 @@ namespace
 template<class T>
 int devAlloc(nmpc_hip_cgmres_solver * h, T ** p, size_t count)
 {
-  CG_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T)));
   h->allocs.push_back(*p);
-  CG_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
+  NMPC_CAPI_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(T)));
   return NMPC_HIP_OK;
 }
 
@@ -251,17 +224,17 @@ void applyConfig(nmpc_hip_cgmres_solver * h)
 int launchSetup(nmpc_hip_cgmres_solver * h)
 {
   const size_t B = h->bf.B;
-  CG_TRY(hipMemcpyAsync(h->bf.x, h->d_x_init, B * h->ops->nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  CG_TRY(hipMemcpyAsync(h->bf.u, h->d_u_init, B * h->ops->nuc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  CG_TRY(h->ops->launch_setup(h->bf, h->stream));
+  NMPC_CAPI_TRY(hipMemcpyAsync(h->bf.x, h->d_x_init, B * h->ops->nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  NMPC_CAPI_TRY(hipMemcpyAsync(h->bf.u, h->d_u_init, B * h->ops->nuc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  NMPC_CAPI_TRY(h->ops->launch_setup(h->bf, h->stream));
   return NMPC_HIP_OK;
 }
 
 int finishTimed(nmpc_hip_cgmres_solver * h)
 {
-  CG_TRY(hipEventRecord(h->ev1, h->stream));
-  CG_TRY(hipEventSynchronize(h->ev1));
-  CG_TRY(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  NMPC_CAPI_TRY(hipEventRecord(h->ev1, h->stream));
+  NMPC_CAPI_TRY(hipEventSynchronize(h->ev1));
+  NMPC_CAPI_TRY(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   return NMPC_HIP_OK;
 }
 
@@ -504,13 +477,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[C/GMRES] horizon_divide_num and batch must be positive");
     }
-    {
-      const int rc = checkDevice(device);
-      if(rc != NMPC_HIP_OK)
-      {
-        return rc;
-      }
-    }
+    NMPC_CAPI_CHECK(capi::checkDevice<Family>(device));
     auto * h = new nmpc_hip_cgmres_solver();
     h->ops = m;
     h->device = device;
@@ -635,10 +602,10 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[C/GMRES] param blob size mismatch (param_bytes, or batch * param_bytes per instance)");
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     void * p = nullptr;
-    CG_TRY(hipMalloc(&p, bytes));
+    NMPC_CAPI_TRY(hipMalloc(&p, bytes));
     if(hipMemcpy(p, params, bytes, hipMemcpyHostToDevice) != hipSuccess)
     {
       (void)hipFree(p);
@@ -657,8 +624,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     const size_t B = h->bf.B;
     for(int k = 0; k < 2; k++)
     {
@@ -670,8 +637,8 @@ extern "C"
       const size_t E = k == 0 ? h->ops->nx : h->ops->nuc;
       std::vector<double> d(B * E);
       toDevice(src, d.data(), B, E);
-      CG_TRY(hipMemcpy(k == 0 ? h->d_x_init : h->d_u_init, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
-      CG_TRY(hipMemcpy(k == 0 ? h->bf.x : h->bf.u, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
+      NMPC_CAPI_TRY(hipMemcpy(k == 0 ? h->d_x_init : h->d_u_init, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
+      NMPC_CAPI_TRY(hipMemcpy(k == 0 ? h->bf.x : h->bf.u, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     return NMPC_HIP_OK;
   }
@@ -682,8 +649,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipEventRecord(h->ev0, h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev0, h->stream));
     const int rc = launchSetup(h);
     if(rc != NMPC_HIP_OK)
     {
@@ -699,8 +666,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     // the tick times exactly as `for(double t = 0; t <= sim_duration_; t += dt_)` produces them
     std::vector<double> ts;
     for(double t = 0; t <= h->cfg.sim_duration; t += h->cfg.dt)
@@ -715,7 +682,7 @@ extern "C"
     {
       const size_t rows = static_cast<size_t>((n_ticks - 1) / h->cfg.dump_step + 1);
       const size_t doubles = rows * B * (NX + NUC + 1), ints = 2 * rows * B;
-      CG_TRY(hipMalloc(&h->d_logs, doubles * sizeof(double) + ints * sizeof(int)));
+      NMPC_CAPI_TRY(hipMalloc(&h->d_logs, doubles * sizeof(double) + ints * sizeof(int)));
       b.log_x = static_cast<double *>(h->d_logs);
       b.log_u = b.log_x + rows * NX * B;
       b.log_err = b.log_u + rows * NUC * B;
@@ -725,14 +692,14 @@ extern "C"
       // rows an instance does not reach (it stopped on a non-finite value) read NaN / -1
       hipLaunchKernelGGL(cgmres_fill_kernel, dim3(static_cast<unsigned>((doubles + 255) / 256)), dim3(256), 0, h->stream, b.log_x, doubles,
                          std::nan(""));
-      CG_TRY(hipGetLastError());
-      CG_TRY(hipMemsetAsync(b.log_iters, 0xff, ints * sizeof(int), h->stream));
+      NMPC_CAPI_TRY(hipGetLastError());
+      NMPC_CAPI_TRY(hipMemsetAsync(b.log_iters, 0xff, ints * sizeof(int), h->stream));
       for(size_t r = 0; r < rows; r++)
       {
         h->log_t.push_back(ts[r * h->cfg.dump_step]);
       }
     }
-    CG_TRY(hipEventRecord(h->ev0, h->stream));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev0, h->stream));
     int rc = launchSetup(h);
     if(rc != NMPC_HIP_OK)
     {
@@ -748,7 +715,7 @@ extern "C"
     }
     for(int i0 = 0; i0 < n_ticks; i0 += chunk)
     {
-      CG_TRY(launchRun(h, i0, std::min(chunk, n_ticks - i0), ts[i0]));
+      NMPC_CAPI_TRY(launchRun(h, i0, std::min(chunk, n_ticks - i0), ts[i0]));
     }
     return finishTimed(h);
   }
@@ -764,9 +731,9 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "[C/GMRES] control_input needs setup() first");
     }
-    CG_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    CG_TRY(launchControlInput(h, d_t, d_x, d_next_x, d_u, s));
+    NMPC_CAPI_TRY(launchControlInput(h, d_t, d_x, d_next_x, d_u, s));
     return NMPC_HIP_OK;
   }
 
@@ -780,18 +747,18 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "[C/GMRES] control_input needs setup() first");
     }
-    CG_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const size_t B = h->bf.B, NX = h->ops->nx, NUC = h->ops->nuc;
     double * dt = h->d_ctl;
     double * dx = dt + B;
     double * dnx = dx + B * NX;
     double * du = dnx + B * NX;
-    CG_TRY(hipEventRecord(h->ev0, h->stream));
-    CG_TRY(hipMemcpyAsync(dt, t, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CG_TRY(hipMemcpyAsync(dx, x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CG_TRY(hipMemcpyAsync(dnx, next_x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CG_TRY(launchControlInput(h, dt, dx, dnx, du, h->stream));
-    CG_TRY(hipMemcpyAsync(u, du, B * NUC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev0, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(dt, t, B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(dx, x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(dnx, next_x, B * NX * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(launchControlInput(h, dt, dx, dnx, du, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(u, du, B * NUC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return finishTimed(h);
   }
 
@@ -801,8 +768,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     return NMPC_HIP_OK;
   }
 
@@ -848,8 +815,8 @@ extern "C"
     {
       return NMPC_HIP_OK;
     }
-    CG_TRY(hipSetDevice(h->device));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     if(field == NMPC_HIP_CGMRES_FIELD_LOG_T)
     {
       std::memcpy(out, h->log_t.data(), want);
@@ -880,13 +847,13 @@ extern "C"
     if(is_int)
     {
       std::vector<int> tmp(B * Et);
-      CG_TRY(hipMemcpy(tmp.data(), src, want, hipMemcpyDeviceToHost));
+      NMPC_CAPI_TRY(hipMemcpy(tmp.data(), src, want, hipMemcpyDeviceToHost));
       toBoundary(tmp.data(), static_cast<int *>(out), B, Et);
     }
     else
     {
       std::vector<double> tmp(B * Et);
-      CG_TRY(hipMemcpy(tmp.data(), src, want, hipMemcpyDeviceToHost));
+      NMPC_CAPI_TRY(hipMemcpy(tmp.data(), src, want, hipMemcpyDeviceToHost));
       toBoundary(tmp.data(), static_cast<double *>(out), B, Et);
     }
     return NMPC_HIP_OK;
@@ -899,13 +866,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[C/GMRES] dense_gmres: 1 <= n <= 512, batch >= 1, k_max >= 1, eps >= 0, non-NULL arrays");
     }
-    {
-      const int rc = checkDevice(device);
-      if(rc != NMPC_HIP_OK)
-      {
-        return rc;
-      }
-    }
+    NMPC_CAPI_CHECK(capi::checkDevice<Family>(device));
     const size_t B = batch, N = n;
     const int K = std::min(k_max, n);
     const size_t ws_elems = cg::gmresWorkspaceElems(n, K);
@@ -914,24 +875,24 @@ extern "C"
     toDevice(x, hx.data(), B, N);
     toDevice(b, hws.data(), B, N); // the right-hand side is the workspace's first vector
     DevBuf dA, dx, dws, dit;
-    CG_TRY(hipMalloc(&dA.p, hA.size() * sizeof(double)));
-    CG_TRY(hipMalloc(&dx.p, hx.size() * sizeof(double)));
-    CG_TRY(hipMalloc(&dws.p, ws_elems * B * sizeof(double)));
-    CG_TRY(hipMalloc(&dit.p, 2 * B * sizeof(int)));
-    CG_TRY(hipMemcpy(dA.p, hA.data(), hA.size() * sizeof(double), hipMemcpyHostToDevice));
-    CG_TRY(hipMemcpy(dx.p, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
-    CG_TRY(hipMemset(dws.p, 0, ws_elems * B * sizeof(double)));
-    CG_TRY(hipMemcpy(dws.p, hws.data(), hws.size() * sizeof(double), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMalloc(&dA.p, hA.size() * sizeof(double)));
+    NMPC_CAPI_TRY(hipMalloc(&dx.p, hx.size() * sizeof(double)));
+    NMPC_CAPI_TRY(hipMalloc(&dws.p, ws_elems * B * sizeof(double)));
+    NMPC_CAPI_TRY(hipMalloc(&dit.p, 2 * B * sizeof(int)));
+    NMPC_CAPI_TRY(hipMemcpy(dA.p, hA.data(), hA.size() * sizeof(double), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMemcpy(dx.p, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMemset(dws.p, 0, ws_elems * B * sizeof(double)));
+    NMPC_CAPI_TRY(hipMemcpy(dws.p, hws.data(), hws.size() * sizeof(double), hipMemcpyHostToDevice));
     int * d_it = static_cast<int *>(dit.p);
     hipLaunchKernelGGL(cg::cgmres_gmres_dense_kernel, dim3(static_cast<unsigned>((B + cg::kBlock - 1) / cg::kBlock)), dim3(cg::kBlock), 0,
                        nullptr, batch, n, K, k_max, apply_reorth, eps, static_cast<const double *>(dA.p), static_cast<double *>(dx.p),
                        static_cast<double *>(dws.p), d_it, d_it + B);
-    CG_TRY(hipGetLastError());
-    CG_TRY(hipDeviceSynchronize());
-    CG_TRY(hipMemcpy(hx.data(), dx.p, hx.size() * sizeof(double), hipMemcpyDeviceToHost));
+    NMPC_CAPI_TRY(hipGetLastError());
+    NMPC_CAPI_TRY(hipDeviceSynchronize());
+    NMPC_CAPI_TRY(hipMemcpy(hx.data(), dx.p, hx.size() * sizeof(double), hipMemcpyDeviceToHost));
     toBoundary(hx.data(), x, B, N);
     std::vector<int> it(2 * B);
-    CG_TRY(hipMemcpy(it.data(), dit.p, it.size() * sizeof(int), hipMemcpyDeviceToHost));
+    NMPC_CAPI_TRY(hipMemcpy(it.data(), dit.p, it.size() * sizeof(int), hipMemcpyDeviceToHost));
     if(iters)
     {
       std::copy(it.begin(), it.begin() + B, iters);
@@ -950,7 +911,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument or n_points < 1");
     }
-    CG_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const size_t P = n_points, NX = h->ops->nx, NUC = h->ops->nuc;
     const size_t sizes[8] = {P, P * NX, P * NUC, P * NX, P * NX, P * NX, P * NX, P * NUC};
     size_t total = 0;
@@ -959,7 +920,7 @@ extern "C"
       total += s;
     }
     DevBuf d;
-    CG_TRY(hipMalloc(&d.p, total * sizeof(double)));
+    NMPC_CAPI_TRY(hipMalloc(&d.p, total * sizeof(double)));
     double * p[8];
     p[0] = static_cast<double *>(d.p);
     for(int i = 1; i < 8; i++)
@@ -968,16 +929,16 @@ extern "C"
     }
     const double * in[4] = {t, x, u, lmd};
     double * outs[4] = {dotx, dotlmd, dphidx, dhdu};
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     for(int i = 0; i < 4; i++)
     {
-      CG_TRY(hipMemcpy(p[i], in[i], sizes[i] * sizeof(double), hipMemcpyHostToDevice));
+      NMPC_CAPI_TRY(hipMemcpy(p[i], in[i], sizes[i] * sizeof(double), hipMemcpyHostToDevice));
     }
-    CG_TRY(h->ops->launch_model_eval(h->bf, n_points, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], h->stream));
-    CG_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(h->ops->launch_model_eval(h->bf, n_points, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     for(int i = 0; i < 4; i++)
     {
-      CG_TRY(hipMemcpy(outs[i], p[4 + i], sizes[4 + i] * sizeof(double), hipMemcpyDeviceToHost));
+      NMPC_CAPI_TRY(hipMemcpy(outs[i], p[4 + i], sizes[4 + i] * sizeof(double), hipMemcpyDeviceToHost));
     }
     return NMPC_HIP_OK;
   }
@@ -994,6 +955,6 @@ extern "C"
 
   const char * nmpc_hip_cgmres_last_error(void)
   {
-    return g_cgmres_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 }

@@ -11,38 +11,18 @@
 #define NMPC_AMD_FMPC_COMMON_KERNELS // the problem-independent kernels of fmpc_kernels.hpp live in this translation unit
 #include <nmpc_amd/hip/fmpc_ops.hpp>
 
+#include <nmpc_amd/hip/capi_core.hpp>
+
+namespace capi = nmpc_amd::hip::capi;
 using nmpc_amd::hip::FmpcBuffers;
 using nmpc_amd::hip::FmpcOps;
 
 namespace
 {
-thread_local std::string g_fmpc_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family // (nmpc_hip_fmpc_create keeps its device check in line: no noun)
 {
-  g_fmpc_last_error = msg;
-  return code;
-}
-
-#define FMPC_TRY(expr)                                                                    \
-  do                                                                                      \
-  {                                                                                       \
-    hipError_t e_ = (expr);                                                               \
-    if(e_ != hipSuccess)                                                                  \
-    {                                                                                     \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    }                                                                                     \
-  } while(0)
-
-#define FMPC_CHECK(expr)          \
-  do                              \
-  {                               \
-    int rc_ = (expr);             \
-    if(rc_ != NMPC_HIP_OK)        \
-    {                             \
-      return rc_;                 \
-    }                             \
-  } while(0)
+};
+constexpr auto fail = capi::fail<Family>;
 
 std::vector<const FmpcOps *> & registry()
 {
@@ -181,17 +161,17 @@ namespace
 {
 int devAlloc(nmpc_hip_fmpc_solver * h, double ** p, size_t count)
 {
-  FMPC_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(double)));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(double)));
   h->allocs.push_back(*p);
-  FMPC_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(double)));
+  NMPC_CAPI_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(double)));
   return NMPC_HIP_OK;
 }
 
 int devAllocInt(nmpc_hip_fmpc_solver * h, int ** p, size_t count)
 {
-  FMPC_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(int)));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(int)));
   h->allocs.push_back(*p);
-  FMPC_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(int)));
+  NMPC_CAPI_TRY(hipMemset(*p, 0, std::max<size_t>(count, 1) * sizeof(int)));
   return NMPC_HIP_OK;
 }
 
@@ -203,11 +183,11 @@ int ensureStage(nmpc_hip_fmpc_solver * h, size_t bytes)
   }
   if(h->d_stage)
   {
-    FMPC_TRY(hipFree(h->d_stage));
+    NMPC_CAPI_TRY(hipFree(h->d_stage));
     h->d_stage = nullptr;
     h->stage_bytes = 0;
   }
-  FMPC_TRY(hipMalloc(reinterpret_cast<void **>(&h->d_stage), bytes));
+  NMPC_CAPI_TRY(hipMalloc(reinterpret_cast<void **>(&h->d_stage), bytes));
   h->stage_bytes = bytes;
   return NMPC_HIP_OK;
 }
@@ -248,12 +228,12 @@ int timeMark(nmpc_hip_fmpc_solver * h, hipStream_t stream, int kernel_class, boo
   if(h->kev_used == h->kev.size())
   {
     hipEvent_t e = nullptr;
-    FMPC_TRY(hipEventCreate(&e));
+    NMPC_CAPI_TRY(hipEventCreate(&e));
     h->kev.push_back(e);
     h->kev_class.push_back(0);
   }
   h->kev_class[h->kev_used] = begin ? kernel_class : -1;
-  FMPC_TRY(hipEventRecord(h->kev[h->kev_used], stream));
+  NMPC_CAPI_TRY(hipEventRecord(h->kev[h->kev_used], stream));
   h->kev_used++;
   return NMPC_HIP_OK;
 }
@@ -261,10 +241,10 @@ int timeMark(nmpc_hip_fmpc_solver * h, hipStream_t stream, int kernel_class, boo
 #define FMPC_TIMED(h, stream, kernel_class, launch)           \
   do                                                          \
   {                                                           \
-    FMPC_CHECK(timeMark(h, stream, kernel_class, true));      \
+    NMPC_CAPI_CHECK(timeMark(h, stream, kernel_class, true));      \
     launch;                                                   \
-    FMPC_TRY(hipGetLastError());                              \
-    FMPC_CHECK(timeMark(h, stream, kernel_class, false));     \
+    NMPC_CAPI_TRY(hipGetLastError());                              \
+    NMPC_CAPI_CHECK(timeMark(h, stream, kernel_class, false));     \
   } while(0)
 
 /** The kernel sequence of FmpcSolver::solve (FmpcSolver.hpp:156-255) on `stream`. */
@@ -280,11 +260,11 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
              hipLaunchKernelGGL(nmpc_amd::hip::fmpc_begin_kernel, dim3(nb), dim3(64), 0, stream, buf));
   if(dims)
   {
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, FMPC_TRY(ops->launch_dims(buf, h->d_dims, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, NMPC_CAPI_TRY(ops->launch_dims(buf, h->d_dims, stream)));
   }
   if(h->cfg.init_complementary_variable)
   {
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, FMPC_TRY(ops->launch_init_complementary(buf, dims, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_OTHER, NMPC_CAPI_TRY(ops->launch_init_complementary(buf, dims, stream)));
   }
   if(dims)
   {
@@ -317,13 +297,13 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
                    hipLaunchKernelGGL(nmpc_amd::hip::fmpc_barrier_kernel, dim3(nb), dim3(64 * nmpc_amd::hip::fmpc::kSlices), 0, stream, buf,
                                       iter));
       }
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_COEFF, FMPC_TRY(ops->launch_coeff(buf, dims, stream)));
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_COEFF, NMPC_CAPI_TRY(ops->launch_coeff(buf, dims, stream)));
     }
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_RICCATI, FMPC_TRY(ops->launch_riccati(buf, iter, stream)));
-    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_DELTA, FMPC_TRY(ops->launch_delta(buf, dims, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_RICCATI, NMPC_CAPI_TRY(ops->launch_riccati(buf, iter, stream)));
+    FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_DELTA, NMPC_CAPI_TRY(ops->launch_delta(buf, dims, stream)));
     if(tail)
     {
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE, FMPC_TRY(ops->launch_tail(buf, iter, iter == h->cfg.max_iter ? 1 : 0, stream)));
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_UPDATE, NMPC_CAPI_TRY(ops->launch_tail(buf, iter, iter == h->cfg.max_iter ? 1 : 0, stream)));
       continue;
     }
     FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_STEP_LENGTH,
@@ -331,7 +311,7 @@ int enqueueSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
                                   buf, iter));
     if(h->cfg.enable_line_search)
     {
-      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_LINE_SEARCH, FMPC_TRY(ops->launch_line_search(buf, dims, iter, stream)));
+      FMPC_TIMED(h, stream, NMPC_HIP_FMPC_KERNEL_LINE_SEARCH, NMPC_CAPI_TRY(ops->launch_line_search(buf, dims, iter, stream)));
     }
     if(dims)
     {
@@ -364,7 +344,7 @@ int launchSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
   }
   if(!h->graph_exec)
   {
-    FMPC_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    NMPC_CAPI_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     const int rc = enqueueSolve(h, h->stream);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(h->stream, &g);
@@ -376,11 +356,11 @@ int launchSolve(nmpc_hip_fmpc_solver * h, hipStream_t stream)
       }
       return rc;
     }
-    FMPC_TRY(e);
+    NMPC_CAPI_TRY(e);
     h->graph = g;
-    FMPC_TRY(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
+    NMPC_CAPI_TRY(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
   }
-  FMPC_TRY(hipGraphLaunch(h->graph_exec, stream));
+  NMPC_CAPI_TRY(hipGraphLaunch(h->graph_exec, stream));
   return NMPC_HIP_OK;
 }
 
@@ -440,16 +420,16 @@ int uploadField(nmpc_hip_fmpc_solver * h, const double * src, double * dst, int 
   const double * d_src = src;
   if(!on_device)
   {
-    FMPC_CHECK(ensureStage(h, count * sizeof(double)));
-    FMPC_TRY(hipMemcpyAsync(h->d_stage, src, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_CHECK(ensureStage(h, count * sizeof(double)));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_stage, src, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
     d_src = h->d_stage;
   }
   hipLaunchKernelGGL(nmpc_amd::hip::fmpc_transpose_kernel, fmpcTransposeGrid(h->buf.B, steps, E, 1), dim3(256), 0, h->stream, d_src, dst,
                      h->buf.B, steps, E, 1);
-  FMPC_TRY(hipGetLastError());
+  NMPC_CAPI_TRY(hipGetLastError());
   if(!on_device)
   {
-    FMPC_TRY(hipStreamSynchronize(h->stream)); // the staging buffer is reused by the next field
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream)); // the staging buffer is reused by the next field
   }
   return NMPC_HIP_OK;
 }
@@ -463,22 +443,22 @@ int ingest(nmpc_hip_fmpc_solver * h, const double * t, const double * x0, bool o
   }
   if(t)
   {
-    FMPC_TRY(hipMemcpyAsync(h->d_t0, t, static_cast<size_t>(B) * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_t0, t, static_cast<size_t>(B) * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                             stream));
   }
   else
   {
-    FMPC_TRY(hipMemsetAsync(h->d_t0, 0, static_cast<size_t>(B) * sizeof(double), stream));
+    NMPC_CAPI_TRY(hipMemsetAsync(h->d_t0, 0, static_cast<size_t>(B) * sizeof(double), stream));
   }
   const double * d_src = x0;
   if(!on_device)
   {
-    FMPC_CHECK(ensureStage(h, static_cast<size_t>(B) * N * sizeof(double)));
-    FMPC_TRY(hipMemcpyAsync(h->d_stage, x0, static_cast<size_t>(B) * N * sizeof(double), hipMemcpyHostToDevice, stream));
+    NMPC_CAPI_CHECK(ensureStage(h, static_cast<size_t>(B) * N * sizeof(double)));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_stage, x0, static_cast<size_t>(B) * N * sizeof(double), hipMemcpyHostToDevice, stream));
     d_src = h->d_stage;
   }
   hipLaunchKernelGGL(nmpc_amd::hip::fmpc_transpose_kernel, fmpcTransposeGrid(B, 1, N, 1), dim3(256), 0, stream, d_src, h->d_x0, B, 1, N, 1);
-  FMPC_TRY(hipGetLastError());
+  NMPC_CAPI_TRY(hipGetLastError());
   return NMPC_HIP_OK;
 }
 } // namespace
@@ -631,6 +611,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FMPC] horizon_steps and batch must be positive");
     }
+    // (capi::checkDevice, in line: as a call it changes which weak symbols this translation unit emits out of line)
     int n_dev = 0;
     const hipError_t e = hipGetDeviceCount(&n_dev);
     if(e != hipSuccess || n_dev <= 0)
@@ -642,7 +623,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
     }
-    FMPC_TRY(hipSetDevice(device));
+    NMPC_CAPI_TRY(hipSetDevice(device));
     auto * h = new nmpc_hip_fmpc_solver();
     h->ops = m;
     h->device = device;
@@ -763,12 +744,12 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FMPC] max_iter must be non-negative");
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     if(cfg->max_iter > h->trace_rows)
     {
       double * p = nullptr;
-      FMPC_CHECK(devAlloc(h, &p, static_cast<size_t>(h->buf.B) * cfg->max_iter * NMPC_HIP_FMPC_NTRACE));
+      NMPC_CAPI_CHECK(devAlloc(h, &p, static_cast<size_t>(h->buf.B) * cfg->max_iter * NMPC_HIP_FMPC_NTRACE));
       h->buf.trace = p; // the old buffer stays in allocs until destroy
       h->trace_rows = cfg->max_iter;
     }
@@ -811,17 +792,17 @@ extern "C"
         }
       }
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     if(need != h->problems_bytes)
     {
-      FMPC_TRY(hipFree(h->d_problems));
+      NMPC_CAPI_TRY(hipFree(h->d_problems));
       h->d_problems = nullptr;
-      FMPC_TRY(hipMalloc(&h->d_problems, need));
+      NMPC_CAPI_TRY(hipMalloc(&h->d_problems, need));
       h->problems_bytes = need;
       dropGraph(h);
     }
-    FMPC_TRY(hipMemcpy(h->d_problems, params, need, hipMemcpyHostToDevice));
+    NMPC_CAPI_TRY(hipMemcpy(h->d_problems, params, need, hipMemcpyHostToDevice));
     std::memcpy(h->host_problem.data(), params, pb);
     if(h->buf.own_problems != (per_instance ? 1 : 0))
     {
@@ -852,22 +833,22 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(waitLastSolve(h));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(waitLastSolve(h));
     const FmpcBuffers & b = h->buf;
-    FMPC_CHECK(uploadField(h, x, b.x, b.T + 1, b.N, on_device));
-    FMPC_CHECK(uploadField(h, u, b.u, b.T, b.M, on_device));
-    FMPC_CHECK(uploadField(h, lambda, b.lam, b.T + 1, b.N, on_device));
-    FMPC_CHECK(uploadField(h, s, b.s, b.T, b.G, on_device));
-    FMPC_CHECK(uploadField(h, nu, b.nu, b.T, b.G, on_device));
+    NMPC_CAPI_CHECK(uploadField(h, x, b.x, b.T + 1, b.N, on_device));
+    NMPC_CAPI_CHECK(uploadField(h, u, b.u, b.T, b.M, on_device));
+    NMPC_CAPI_CHECK(uploadField(h, lambda, b.lam, b.T + 1, b.N, on_device));
+    NMPC_CAPI_CHECK(uploadField(h, s, b.s, b.T, b.G, on_device));
+    NMPC_CAPI_CHECK(uploadField(h, nu, b.nu, b.T, b.G, on_device));
     if(barrier_eps)
     {
-      FMPC_TRY(hipMemcpyAsync(b.barrier_eps, barrier_eps, static_cast<size_t>(b.B) * sizeof(double),
+      NMPC_CAPI_TRY(hipMemcpyAsync(b.barrier_eps, barrier_eps, static_cast<size_t>(b.B) * sizeof(double),
                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
     if(!on_device) // device sources: asynchronous on the solver's stream, ordered before the next solve on it
     {
-      FMPC_TRY(hipStreamSynchronize(h->stream));
+      NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     }
     return NMPC_HIP_OK;
   }
@@ -878,7 +859,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FMPC_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const FmpcBuffers & b = h->buf;
     const size_t B = b.B, T = b.T;
     struct
@@ -893,10 +874,10 @@ extern "C"
       if(f.n > 0)
       {
         hipLaunchKernelGGL(fmpc_fill_kernel, dim3(blocks(f.n, 256)), dim3(256), 0, h->stream, f.p, f.n, f.v);
-        FMPC_TRY(hipGetLastError());
+        NMPC_CAPI_TRY(hipGetLastError());
       }
     }
-    FMPC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     return NMPC_HIP_OK;
   }
 
@@ -906,12 +887,12 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FMPC_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    FMPC_TRY(hipEventRecord(h->ev0, st));
-    FMPC_CHECK(ingest(h, d_t, d_x0, true, st));
-    FMPC_CHECK(launchSolve(h, st));
-    FMPC_TRY(hipEventRecord(h->ev1, st));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev0, st));
+    NMPC_CAPI_CHECK(ingest(h, d_t, d_x0, true, st));
+    NMPC_CAPI_CHECK(launchSolve(h, st));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev1, st));
     h->timed = true;
     h->solved = true;
     h->solved_max_iter = h->buf.max_iter;
@@ -925,8 +906,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(hipDeviceSynchronize());
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipDeviceSynchronize());
     return NMPC_HIP_OK;
   }
 
@@ -936,18 +917,18 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(hipEventRecord(h->ev0, h->stream));
-    FMPC_CHECK(ingest(h, t, x0, false, h->stream));
-    FMPC_CHECK(launchSolve(h, h->stream));
-    FMPC_TRY(hipEventRecord(h->ev1, h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev0, h->stream));
+    NMPC_CAPI_CHECK(ingest(h, t, x0, false, h->stream));
+    NMPC_CAPI_CHECK(launchSolve(h, h->stream));
+    NMPC_CAPI_TRY(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     h->solved = true;
     h->solved_max_iter = h->buf.max_iter;
     h->solved_trace = h->buf.trace;
     std::vector<int> status(h->buf.B);
-    FMPC_TRY(hipMemcpyAsync(status.data(), h->buf.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    FMPC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(status.data(), h->buf.status, status.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     for(int b = 0; b < h->buf.B; b++)
     {
       if(status[b] == NMPC_HIP_FMPC_STATUS_INVALID_VARIABLE)
@@ -965,7 +946,7 @@ extern "C"
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
     FieldInfo fi;
-    FMPC_CHECK(fieldInfo(h, field, &fi));
+    NMPC_CAPI_CHECK(fieldInfo(h, field, &fi));
     *bytes = static_cast<size_t>(h->buf.B) * fi.steps * fi.E * (fi.is_int ? sizeof(int) : sizeof(double));
     return NMPC_HIP_OK;
   }
@@ -977,14 +958,14 @@ extern "C"
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
     FieldInfo fi;
-    FMPC_CHECK(fieldInfo(h, field, &fi));
+    NMPC_CAPI_CHECK(fieldInfo(h, field, &fi));
     const size_t count = static_cast<size_t>(h->buf.B) * fi.steps * fi.E;
     if(bytes != count * (fi.is_int ? sizeof(int) : sizeof(double)))
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FMPC] field size mismatch");
     }
-    FMPC_TRY(hipSetDevice(h->device));
-    FMPC_TRY(waitLastSolve(h));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(waitLastSolve(h));
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if(count == 0)
     {
@@ -993,19 +974,19 @@ extern "C"
     if(fi.is_int)
     {
       const int * src = field == NMPC_HIP_FMPC_FIELD_STATUS ? h->buf.status : h->buf.iters;
-      FMPC_TRY(hipMemcpyAsync(out, src, bytes, kind, h->stream));
-      FMPC_TRY(hipStreamSynchronize(h->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(out, src, bytes, kind, h->stream));
+      NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
       return NMPC_HIP_OK;
     }
     if(field == NMPC_HIP_FMPC_FIELD_TRACE || (fi.steps == 1 && fi.E == 1 && fi.gain_offset < 0))
     {
-      FMPC_TRY(hipMemcpyAsync(out, fi.dev, bytes, kind, h->stream)); // already instance-major
-      FMPC_TRY(hipStreamSynchronize(h->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(out, fi.dev, bytes, kind, h->stream)); // already instance-major
+      NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
       return NMPC_HIP_OK;
     }
     // [steps][E][B] -> [B][steps][E], through the staging buffer (twice its size for gain fields: gather, then transpose)
     const bool gain = fi.gain_offset >= 0;
-    FMPC_CHECK(ensureStage(h, bytes * (gain ? 2 : 1) + (on_device ? 0 : 0)));
+    NMPC_CAPI_CHECK(ensureStage(h, bytes * (gain ? 2 : 1) + (on_device ? 0 : 0)));
     double * d_t = h->d_stage;
     const double * src = fi.dev;
     if(gain)
@@ -1013,18 +994,18 @@ extern "C"
       double * d_g = h->d_stage + count;
       hipLaunchKernelGGL(fmpc_gather_gain_kernel, dim3(blocks(count, 256)), dim3(256), 0, h->stream, h->buf.gain, d_g, h->buf.B, fi.steps,
                          fi.E, h->buf.gain_stride, fi.gain_offset);
-      FMPC_TRY(hipGetLastError());
+      NMPC_CAPI_TRY(hipGetLastError());
       src = d_g;
     }
     double * dst = on_device ? static_cast<double *>(out) : d_t;
     hipLaunchKernelGGL(nmpc_amd::hip::fmpc_transpose_kernel, fmpcTransposeGrid(h->buf.B, fi.steps, fi.E, 0), dim3(256), 0, h->stream, src,
                        dst, h->buf.B, fi.steps, fi.E, 0);
-    FMPC_TRY(hipGetLastError());
+    NMPC_CAPI_TRY(hipGetLastError());
     if(!on_device)
     {
-      FMPC_TRY(hipMemcpyAsync(out, d_t, bytes, hipMemcpyDeviceToHost, h->stream));
+      NMPC_CAPI_TRY(hipMemcpyAsync(out, d_t, bytes, hipMemcpyDeviceToHost, h->stream));
     }
-    FMPC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     return NMPC_HIP_OK;
   }
 
@@ -1040,9 +1021,9 @@ extern "C"
     }
     if(h->timed)
     {
-      FMPC_TRY(hipSetDevice(h->device));
-      FMPC_TRY(hipEventSynchronize(h->ev1));
-      FMPC_TRY(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+      NMPC_CAPI_TRY(hipSetDevice(h->device));
+      NMPC_CAPI_TRY(hipEventSynchronize(h->ev1));
+      NMPC_CAPI_TRY(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
       h->timed = false;
     }
     *ms = h->last_ms;
@@ -1059,7 +1040,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "[FMPC] the last solve was not run with config.time_kernels = 1");
     }
-    FMPC_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     for(int k = 0; k < NMPC_HIP_FMPC_NKERNELS; k++)
     {
       ms[k] = 0;
@@ -1067,12 +1048,12 @@ extern "C"
     }
     if(h->kev_used > 0)
     {
-      FMPC_TRY(hipEventSynchronize(h->kev[h->kev_used - 1]));
+      NMPC_CAPI_TRY(hipEventSynchronize(h->kev[h->kev_used - 1]));
     }
     for(size_t k = 0; k + 1 < h->kev_used; k += 2)
     {
       float t = 0;
-      FMPC_TRY(hipEventElapsedTime(&t, h->kev[k], h->kev[k + 1]));
+      NMPC_CAPI_TRY(hipEventElapsedTime(&t, h->kev[k], h->kev[k + 1]));
       ms[h->kev_class[k]] += t;
       launches[h->kev_class[k]]++;
     }
@@ -1102,7 +1083,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FMPC] n_ticks, sim_substeps and sim_dt must be positive");
     }
-    FMPC_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const int B = h->buf.B, N = h->buf.N, M = h->buf.M;
     const size_t nt = n_ticks;
     double *d_xlog = nullptr, *d_ulog = nullptr, *d_klog = nullptr;
@@ -1165,12 +1146,12 @@ extern "C"
         return NMPC_HIP_OK;
       }
       const size_t count = static_cast<size_t>(B) * steps * E;
-      FMPC_CHECK(ensureStage(h, count * sizeof(double)));
+      NMPC_CAPI_CHECK(ensureStage(h, count * sizeof(double)));
       hipLaunchKernelGGL(nmpc_amd::hip::fmpc_transpose_kernel, fmpcTransposeGrid(B, steps, E, 0), dim3(256), 0, h->stream, d_src, h->d_stage,
                          B, steps, E, 0);
-      FMPC_TRY(hipGetLastError());
-      FMPC_TRY(hipMemcpyAsync(host, h->d_stage, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      FMPC_TRY(hipStreamSynchronize(h->stream));
+      NMPC_CAPI_TRY(hipGetLastError());
+      NMPC_CAPI_TRY(hipMemcpyAsync(host, h->d_stage, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
       return NMPC_HIP_OK;
     };
     rc = fetch(d_xlog, x_log, n_ticks, N);
@@ -1303,13 +1284,13 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_NOT_SOLVED, "[FMPC] no solve yet");
     }
-    FMPC_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
     const int B = h->buf.B, T = h->buf.T;
     std::vector<int> dev(static_cast<size_t>(2) * T * B);
     if(h->d_dims)
     {
-      FMPC_TRY(hipStreamSynchronize(h->stream));
-      FMPC_TRY(hipMemcpy(dev.data(), h->d_dims, dev.size() * sizeof(int), hipMemcpyDeviceToHost));
+      NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
+      NMPC_CAPI_TRY(hipMemcpy(dev.data(), h->d_dims, dev.size() * sizeof(int), hipMemcpyDeviceToHost));
     }
     else
     {
@@ -1333,7 +1314,7 @@ extern "C"
       }
       if(on_device)
       {
-        FMPC_TRY(hipMemcpy(out, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+        NMPC_CAPI_TRY(hipMemcpy(out, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
       }
       else
       {
@@ -1345,6 +1326,6 @@ extern "C"
 
   const char * nmpc_hip_fmpc_last_error(void)
   {
-    return g_fmpc_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 }

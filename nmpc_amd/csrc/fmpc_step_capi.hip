@@ -8,8 +8,10 @@
 #include <string>
 #include <vector>
 
+#include <nmpc_amd/hip/capi_core.hpp>
 #include <nmpc_amd/hip/fmpc_step_kernels.hpp>
 
+namespace capi = nmpc_amd::hip::capi;
 namespace fs = nmpc_amd::hip::fmpc_step;
 
 static_assert(NMPC_HIP_FMPC_STEP_MAX_DIM == fs::kMaxDim && NMPC_HIP_FMPC_STEP_MAX_INEQ == fs::kMaxIneq,
@@ -22,59 +24,23 @@ static_assert(int(NMPC_HIP_FMPC_STEP_SUCCEEDED) == fs::kSucceeded && int(NMPC_HI
 
 namespace
 {
-thread_local std::string g_fmpc_step_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family
 {
-  g_fmpc_step_last_error = msg;
-  return code;
-}
-
-#define FS_TRY(expr)                                                                      \
-  do                                                                                      \
-  {                                                                                       \
-    hipError_t e_ = (expr);                                                               \
-    if(e_ != hipSuccess)                                                                  \
-    {                                                                                     \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    }                                                                                     \
-  } while(0)
-
-int checkDevice(int device)
-{
-  int n_dev = 0;
-  const hipError_t e = hipGetDeviceCount(&n_dev);
-  if(e != hipSuccess || n_dev <= 0)
-  {
-    return fail(NMPC_HIP_ERR_NO_DEVICE, std::string("no HIP device available (") + hipGetErrorString(e) +
-                                            "): the FMPC step solver has no CPU fallback");
-  }
-  if(device < 0 || device >= n_dev)
-  {
-    return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
-  }
-  FS_TRY(hipSetDevice(device));
-  return NMPC_HIP_OK;
-}
-
-/** One input array: the caller's device pointer, or the handle's staging copy of a host array. */
-struct Input
-{
-  const double * ptr = nullptr; // what the kernel reads
-  double * stage = nullptr; // owned
-  size_t stage_count = 0;
+  static constexpr const char * tag = "[FmpcStep]";
+  static constexpr const char * noun = "the FMPC step solver";
+  static constexpr const char * prefix = "nmpc_hip_fmpc_step";
 };
+constexpr auto fail = capi::fail<Family>;
+using capi::Input;
 } // namespace
 
-struct nmpc_hip_fmpc_step_solver
+struct nmpc_hip_fmpc_step_solver : capi::HandleCore<Family>
 {
   int n = 0, m = 0, g = 0, T = 0;
   size_t B = 0;
-  int device = 0;
   nmpc_hip_fmpc_step_config cfg;
   bool have_linearisation = false, have_variable = false, have_dims = false, stepped = false;
   int total_ineq_dim = 0;
-  std::vector<void *> allocs;
   Input A, Bm, C, D, Lx, Lu, Lxx, Luu, Lxu, f, gv, LxT, LxxT, cur_x;
   int *d_mdims = nullptr, *d_gdims = nullptr;
   double *d_x = nullptr, *d_u = nullptr, *d_lam = nullptr, *d_s = nullptr, *d_nu = nullptr, *d_eps = nullptr; // the variable
@@ -84,70 +50,10 @@ struct nmpc_hip_fmpc_step_solver
   {
     return fs::OutputLayout(B, T, n, m, g);
   }
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
 };
 
 namespace
 {
-template<class T>
-int devAlloc(nmpc_hip_fmpc_step_solver * h, T ** p, size_t count, const char * what)
-{
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
-  if(e != hipSuccess)
-  {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(NMPC_HIP_ERR_RUNTIME, std::string("[FmpcStep] device allocation of ") + std::to_string(bytes) + " bytes for " + what
-                                          + " failed: " + hipGetErrorString(e));
-  }
-  h->allocs.push_back(*p);
-  // on the handle's stream, and waited for: a hipMemset on the null stream is not ordered against the copies that follow on the
-  // handle's (non-blocking) stream
-  FS_TRY(hipMemsetAsync(*p, 0, bytes, h->stream));
-  FS_TRY(hipStreamSynchronize(h->stream));
-  return NMPC_HIP_OK;
-}
-
-/** `in` <- the caller's array of `count` doubles: in place (device) or through the staging copy (host), on the handle's stream. */
-int setInput(nmpc_hip_fmpc_step_solver * h, Input & in, const double * src, size_t count, int on_device, const char * what)
-{
-  if(count == 0 || !src)
-  {
-    in.ptr = nullptr;
-    return NMPC_HIP_OK;
-  }
-  if(on_device)
-  {
-    in.ptr = src;
-    return NMPC_HIP_OK;
-  }
-  if(in.stage_count < count)
-  {
-    const int rc_ = devAlloc(h, &in.stage, count, what);
-    if(rc_ != NMPC_HIP_OK)
-    {
-      return rc_;
-    }
-    in.stage_count = count;
-  }
-  FS_TRY(hipMemcpyAsync(in.stage, src, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  in.ptr = in.stage;
-  return NMPC_HIP_OK;
-}
-
-int waitForOtherStream(nmpc_hip_fmpc_step_solver * h)
-{
-  if(h->last_stream && h->last_stream != h->stream)
-  {
-    FS_TRY(hipStreamSynchronize(h->last_stream)); // a step_device on another stream may still be using the buffers
-  }
-  return NMPC_HIP_OK;
-}
-
 int validConfig(const nmpc_hip_fmpc_step_config & c)
 {
   if(std::isnan(c.dt) || std::isnan(c.kkt_error_thre))
@@ -274,15 +180,19 @@ int launchStep(nmpc_hip_fmpc_step_solver * h, hipStream_t s)
                         h->gv.ptr, h->LxT.ptr, h->LxxT.ptr, h->cur_x.ptr, h->have_dims ? h->d_mdims : nullptr,
                         h->have_dims ? h->d_gdims : nullptr, h->d_x, h->d_u, h->d_lam, h->d_s, h->d_nu, h->d_eps, h->d_out_d,
                         h->d_out_i};
-  FS_TRY(hipEventRecord(h->ev0, s));
+  NMPC_CAPI_CHECK(h->beginLaunch(s));
   hipLaunchKernelGGL(fs::fmpc_step_wave_kernel, dim3(static_cast<unsigned>(h->B)), dim3(fs::kWave), fs::ldsBytes(h->n, h->m, h->g), s, buf,
                      p);
-  FS_TRY(hipGetLastError());
-  FS_TRY(hipEventRecord(h->ev1, s));
+  NMPC_CAPI_TRY(hipGetLastError());
+  NMPC_CAPI_CHECK(h->endLaunch(s));
   h->stepped = true;
-  h->last_stream = s;
-  h->timed = true;
   return NMPC_HIP_OK;
+}
+
+/** The VAR fields are there from set_variable on, every other field from the first step on. */
+bool haveField(const nmpc_hip_fmpc_step_solver * h, int field)
+{
+  return isVarField(field) ? h->have_variable : h->stepped;
 }
 } // namespace
 
@@ -311,31 +221,7 @@ extern "C"
     {
       return NMPC_HIP_OK;
     }
-    (void)hipSetDevice(h->device);
-    if(h->last_stream)
-    {
-      (void)hipStreamSynchronize(h->last_stream);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamSynchronize(h->stream);
-    }
-    for(void * p : h->allocs)
-    {
-      (void)hipFree(p);
-    }
-    if(h->ev0)
-    {
-      (void)hipEventDestroy(h->ev0);
-    }
-    if(h->ev1)
-    {
-      (void)hipEventDestroy(h->ev1);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamDestroy(h->stream);
-    }
+    h->close();
     delete h;
     return NMPC_HIP_OK;
   }
@@ -373,13 +259,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FmpcStep] batch must be positive: " + std::to_string(batch));
     }
-    {
-      const int rc_ = checkDevice(device);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_CHECK(capi::checkDevice<Family>(device));
     auto * h = new nmpc_hip_fmpc_step_solver();
     h->n = state_dim;
     h->m = input_dim;
@@ -392,17 +272,16 @@ extern "C"
       nmpc_hip_fmpc_step_destroy(h);
       return code;
     };
-    if(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess
-       || hipEventCreate(&h->ev1) != hipSuccess)
+    int rc_ = h->open();
+    if(rc_ != NMPC_HIP_OK)
     {
-      return cleanup(fail(NMPC_HIP_ERR_HIP, "stream / event creation failed"));
+      return cleanup(rc_);
     }
     const size_t T = horizon_steps, B = batch, n = state_dim, m = input_dim, g = ineq_dim;
-    int rc_ = NMPC_HIP_OK;
     auto A = [&](auto ** p, size_t count, const char * what) {
       if(rc_ == NMPC_HIP_OK)
       {
-        rc_ = devAlloc(h, p, count, what);
+        rc_ = h->devAlloc(p, count, what);
       }
     };
     A(&h->d_mdims, T, "the input dimensions");
@@ -492,17 +371,11 @@ extern "C"
       }
       total += gd[i];
     }
-    FS_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
-    FS_TRY(hipMemcpyAsync(h->d_mdims, md.data(), md.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    FS_TRY(hipMemcpyAsync(h->d_gdims, gd.data(), gd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    FS_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_mdims, md.data(), md.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_gdims, gd.data(), gd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->total_ineq_dim = total;
     h->have_dims = true;
     return NMPC_HIP_OK;
@@ -530,20 +403,14 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    FS_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
     const size_t Bn = h->B, n = h->n, m = h->m, gg = h->g, S = h->B * h->T;
     int rc_ = NMPC_HIP_OK;
     auto set = [&](Input & in, const double * src, size_t count, const char * what) {
       if(rc_ == NMPC_HIP_OK)
       {
-        rc_ = setInput(h, in, src, count, on_device, what);
+        rc_ = h->setInput(in, src, count, on_device, what);
       }
     };
     set(h->A, A, S * n * n, "A");
@@ -564,7 +431,7 @@ extern "C"
     {
       return rc_;
     }
-    FS_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->have_linearisation = true;
     return NMPC_HIP_OK;
   }
@@ -582,26 +449,20 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    FS_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
     const size_t B = h->B, n = h->n, m = h->m, g = h->g, T = h->T;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     auto copy = [&](double * dst, const double * src, size_t count) {
       return (count == 0 || !src) ? hipSuccess : hipMemcpyAsync(dst, src, count * sizeof(double), kind, h->stream);
     };
-    FS_TRY(copy(h->d_x, x, B * (T + 1) * n));
-    FS_TRY(copy(h->d_u, u, B * T * m));
-    FS_TRY(copy(h->d_lam, lambda, B * (T + 1) * n));
-    FS_TRY(copy(h->d_s, s, B * T * g));
-    FS_TRY(copy(h->d_nu, nu, B * T * g));
-    FS_TRY(copy(h->d_eps, barrier_eps, B));
-    FS_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(copy(h->d_x, x, B * (T + 1) * n));
+    NMPC_CAPI_TRY(copy(h->d_u, u, B * T * m));
+    NMPC_CAPI_TRY(copy(h->d_lam, lambda, B * (T + 1) * n));
+    NMPC_CAPI_TRY(copy(h->d_s, s, B * T * g));
+    NMPC_CAPI_TRY(copy(h->d_nu, nu, B * T * g));
+    NMPC_CAPI_TRY(copy(h->d_eps, barrier_eps, B));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->have_variable = true;
     return NMPC_HIP_OK;
   }
@@ -612,24 +473,16 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FS_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if(h->last_stream && h->last_stream != s)
-    {
-      FS_TRY(hipStreamSynchronize(h->last_stream)); // the previous step writes the buffers this one writes
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    hipStream_t s = h->streamFor(stream);
+    NMPC_CAPI_CHECK(h->waitBeforeLaunchOn(s)); // the previous step writes the buffers this one writes
     return launchStep(h, s);
   }
 
   int nmpc_hip_fmpc_step_step(nmpc_hip_fmpc_step_handle h)
   {
-    const int rc_ = nmpc_hip_fmpc_step_step_device(h, nullptr);
-    if(rc_ != NMPC_HIP_OK)
-    {
-      return rc_;
-    }
-    FS_TRY(hipStreamSynchronize(h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(nmpc_hip_fmpc_step_step_device(h, nullptr));
+    return h->syncLast();
   }
 
   int nmpc_hip_fmpc_step_synchronize(nmpc_hip_fmpc_step_handle h)
@@ -638,9 +491,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    FS_TRY(hipSetDevice(h->device));
-    FS_TRY(hipStreamSynchronize(h->last_stream ? h->last_stream : h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    return h->syncLast();
   }
 
   int nmpc_hip_fmpc_step_field_bytes(nmpc_hip_fmpc_step_handle h, int field, size_t * bytes)
@@ -654,38 +506,10 @@ extern "C"
 
   int nmpc_hip_fmpc_step_get(nmpc_hip_fmpc_step_handle h, int field, void * out, size_t bytes, int on_device)
   {
-    if(!h)
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
-    }
     size_t want = 0;
-    {
-      const int rc_ = fieldBytes(h, field, &want);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
-    if(bytes != want || (!out && want > 0))
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[FmpcStep] get: bytes must equal nmpc_hip_fmpc_step_field_bytes ("
-                                                     + std::to_string(want) + "), got " + std::to_string(bytes));
-    }
-    if(isVarField(field) ? !h->have_variable : !h->stepped)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[FmpcStep] get needs a step (a set_variable for the VAR fields) first");
-    }
-    FS_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->last_stream ? h->last_stream : h->stream;
-    if(want > 0)
-    {
-      FS_TRY(hipMemcpyAsync(out, fieldPtr(h, field), want, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    }
-    if(!on_device)
-    {
-      FS_TRY(hipStreamSynchronize(s));
-    }
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(capi::beginGet<Family>(h, field, out, bytes, &want, fieldBytes, haveField,
+                                           "get needs a step (a set_variable for the VAR fields)"));
+    return h->copyOut(out, fieldPtr(h, field), want, on_device, capi::kWaitForHostOnly);
   }
 
   int nmpc_hip_fmpc_step_kernel_name(nmpc_hip_fmpc_step_handle h, const char ** name)
@@ -704,18 +528,11 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    if(!h->timed)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[FmpcStep] last_ms needs a step first");
-    }
-    FS_TRY(hipSetDevice(h->device));
-    FS_TRY(hipEventSynchronize(h->ev1));
-    FS_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return NMPC_HIP_OK;
+    return h->lastMs(ms, "last_ms needs a step");
   }
 
   const char * nmpc_hip_fmpc_step_last_error(void)
   {
-    return g_fmpc_step_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 }

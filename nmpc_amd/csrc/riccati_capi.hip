@@ -8,8 +8,10 @@
 #include <string>
 #include <vector>
 
+#include <nmpc_amd/hip/capi_core.hpp>
 #include <nmpc_amd/hip/riccati_kernels.hpp>
 
+namespace capi = nmpc_amd::hip::capi;
 namespace rc = nmpc_amd::hip::riccati;
 
 static_assert(NMPC_HIP_RICCATI_MAX_DIM == rc::kMaxDim, "nmpc_hip_riccati.h and riccati_kernels.hpp disagree");
@@ -19,59 +21,23 @@ static_assert(int(NMPC_HIP_RICCATI_OK) == rc::kStatusOk && int(NMPC_HIP_RICCATI_
 
 namespace
 {
-thread_local std::string g_riccati_last_error;
-
-int fail(int code, const std::string & msg)
+struct Family
 {
-  g_riccati_last_error = msg;
-  return code;
-}
-
-#define RC_TRY(expr)                                                                      \
-  do                                                                                      \
-  {                                                                                       \
-    hipError_t e_ = (expr);                                                               \
-    if(e_ != hipSuccess)                                                                  \
-    {                                                                                     \
-      return fail(NMPC_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    }                                                                                     \
-  } while(0)
-
-int checkDevice(int device)
-{
-  int n_dev = 0;
-  const hipError_t e = hipGetDeviceCount(&n_dev);
-  if(e != hipSuccess || n_dev <= 0)
-  {
-    return fail(NMPC_HIP_ERR_NO_DEVICE, std::string("no HIP device available (") + hipGetErrorString(e) +
-                                            "): the Riccati solver has no CPU fallback");
-  }
-  if(device < 0 || device >= n_dev)
-  {
-    return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "device index out of range");
-  }
-  RC_TRY(hipSetDevice(device));
-  return NMPC_HIP_OK;
-}
-
-/** One input array: the caller's device pointer, or the handle's staging copy of a host array. */
-struct Input
-{
-  const double * ptr = nullptr; // what the kernel reads
-  double * stage = nullptr; // owned
-  size_t stage_count = 0;
+  static constexpr const char * tag = "[Riccati]";
+  static constexpr const char * noun = "the Riccati solver";
+  static constexpr const char * prefix = "nmpc_hip_riccati";
 };
+constexpr auto fail = capi::fail<Family>;
+using capi::Input;
 } // namespace
 
-struct nmpc_hip_riccati_solver
+struct nmpc_hip_riccati_solver : capi::HandleCore<Family>
 {
   int n = 0, m = 0, T = 0;
   size_t B = 0;
-  int device = 0;
   nmpc_hip_riccati_config cfg;
   bool have_derivatives = false, have_inputs = false, have_dims = false, solved = false;
   int limits_per_step = 0;
-  std::vector<void *> allocs;
   Input Fx, Fu, Lx, Lu, Lxx, Luu, Lxu, VxT, VxxT, U, lower, upper, lam, dlam;
   int * d_dims = nullptr;
   double * d_out_d = nullptr; // every real result, placed by rc::OutputLayout
@@ -80,70 +46,10 @@ struct nmpc_hip_riccati_solver
   {
     return rc::OutputLayout(B, T, n, m);
   }
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
 };
 
 namespace
 {
-template<class T>
-int devAlloc(nmpc_hip_riccati_solver * h, T ** p, size_t count, const char * what)
-{
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  const hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
-  if(e != hipSuccess)
-  {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(NMPC_HIP_ERR_RUNTIME, std::string("[Riccati] device allocation of ") + std::to_string(bytes) + " bytes for " + what
-                                          + " failed: " + hipGetErrorString(e));
-  }
-  h->allocs.push_back(*p);
-  // on the handle's stream, and waited for: a hipMemset on the null stream returns before it has run and is not ordered against
-  // the copies that follow on the handle's (non-blocking) stream
-  RC_TRY(hipMemsetAsync(*p, 0, bytes, h->stream));
-  RC_TRY(hipStreamSynchronize(h->stream));
-  return NMPC_HIP_OK;
-}
-
-/** `in` <- the caller's array of `count` doubles: in place (device) or through the staging copy (host), on the handle's stream. */
-int setInput(nmpc_hip_riccati_solver * h, Input & in, const double * src, size_t count, int on_device, const char * what)
-{
-  if(count == 0 || !src)
-  {
-    in.ptr = nullptr;
-    return NMPC_HIP_OK;
-  }
-  if(on_device)
-  {
-    in.ptr = src;
-    return NMPC_HIP_OK;
-  }
-  if(in.stage_count < count)
-  {
-    const int rc_ = devAlloc(h, &in.stage, count, what);
-    if(rc_ != NMPC_HIP_OK)
-    {
-      return rc_;
-    }
-    in.stage_count = count;
-  }
-  RC_TRY(hipMemcpyAsync(in.stage, src, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  in.ptr = in.stage;
-  return NMPC_HIP_OK;
-}
-
-int waitForOtherStream(nmpc_hip_riccati_solver * h)
-{
-  if(h->last_stream && h->last_stream != h->stream)
-  {
-    RC_TRY(hipStreamSynchronize(h->last_stream)); // a solve_device on another stream may still be reading the staging copies
-  }
-  return NMPC_HIP_OK;
-}
-
 int validConfig(const nmpc_hip_riccati_config & c)
 {
   if(c.reg_type != 1 && c.reg_type != 2)
@@ -246,17 +152,20 @@ int launchSolve(nmpc_hip_riccati_solver * h, hipStream_t s)
   const rc::Buffers buf{h->Fx.ptr, h->Fu.ptr, h->Lx.ptr, h->Lu.ptr, h->Lxx.ptr, h->Luu.ptr, h->Lxu.ptr, h->VxT.ptr, h->VxxT.ptr,
                         h->U.ptr, h->lower.ptr, h->upper.ptr, h->lam.ptr, h->dlam.ptr, h->have_dims ? h->d_dims : nullptr,
                         h->d_out_d, h->d_out_i};
-  RC_TRY(hipEventRecord(h->ev0, s));
+  NMPC_CAPI_CHECK(h->beginLaunch(s));
   // qp_retval_ and the free masks of steps without a QP are 0 (the two fields are neighbours in the allocation)
   static_assert(sizeof(int) == sizeof(unsigned), "the free masks share the 32-bit allocation");
-  RC_TRY(hipMemsetAsync(h->d_out_i + h->layout().qp_retval, 0, 2 * h->B * h->T * sizeof(int), s));
+  NMPC_CAPI_TRY(hipMemsetAsync(h->d_out_i + h->layout().qp_retval, 0, 2 * h->B * h->T * sizeof(int), s));
   hipLaunchKernelGGL(rc::riccati_wave_kernel, dim3(static_cast<unsigned>(h->B)), dim3(rc::kWave), rc::ldsBytes(h->n, h->m), s, buf, p);
-  RC_TRY(hipGetLastError());
-  RC_TRY(hipEventRecord(h->ev1, s));
+  NMPC_CAPI_TRY(hipGetLastError());
+  NMPC_CAPI_CHECK(h->endLaunch(s));
   h->solved = true;
-  h->last_stream = s;
-  h->timed = true;
   return NMPC_HIP_OK;
+}
+
+bool solved(const nmpc_hip_riccati_solver * h, int)
+{
+  return h->solved;
 }
 } // namespace
 
@@ -286,31 +195,7 @@ extern "C"
     {
       return NMPC_HIP_OK;
     }
-    (void)hipSetDevice(h->device);
-    if(h->last_stream)
-    {
-      (void)hipStreamSynchronize(h->last_stream);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamSynchronize(h->stream);
-    }
-    for(void * p : h->allocs)
-    {
-      (void)hipFree(p);
-    }
-    if(h->ev0)
-    {
-      (void)hipEventDestroy(h->ev0);
-    }
-    if(h->ev1)
-    {
-      (void)hipEventDestroy(h->ev1);
-    }
-    if(h->stream)
-    {
-      (void)hipStreamDestroy(h->stream);
-    }
+    h->close();
     delete h;
     return NMPC_HIP_OK;
   }
@@ -338,13 +223,7 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[Riccati] batch must be positive: " + std::to_string(batch));
     }
-    {
-      const int rc_ = checkDevice(device);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_CHECK(capi::checkDevice<Family>(device));
     auto * h = new nmpc_hip_riccati_solver();
     h->n = state_dim;
     h->m = input_dim;
@@ -356,17 +235,16 @@ extern "C"
       nmpc_hip_riccati_destroy(h);
       return code;
     };
-    if(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess
-       || hipEventCreate(&h->ev1) != hipSuccess)
+    int rc_ = h->open();
+    if(rc_ != NMPC_HIP_OK)
     {
-      return cleanup(fail(NMPC_HIP_ERR_HIP, "stream / event creation failed"));
+      return cleanup(rc_);
     }
     const size_t T = horizon_steps;
-    int rc_ = NMPC_HIP_OK;
     auto A = [&](auto ** p, size_t count, const char * what) {
       if(rc_ == NMPC_HIP_OK)
       {
-        rc_ = devAlloc(h, p, count, what);
+        rc_ = h->devAlloc(p, count, what);
       }
     };
     A(&h->d_dims, T, "the input dimensions");
@@ -426,16 +304,10 @@ extern "C"
                                                        + " is outside 0 .. " + std::to_string(h->m));
       }
     }
-    RC_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
-    RC_TRY(hipMemcpyAsync(h->d_dims, dims, static_cast<size_t>(h->T) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    RC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
+    NMPC_CAPI_TRY(hipMemcpyAsync(h->d_dims, dims, static_cast<size_t>(h->T) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->have_dims = true;
     return NMPC_HIP_OK;
   }
@@ -456,20 +328,14 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    RC_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
     const size_t B = h->B, n = h->n, m = h->m, S = h->B * h->T;
     int rc_ = NMPC_HIP_OK;
     auto set = [&](Input & in, const double * src, size_t count, const char * what) {
       if(rc_ == NMPC_HIP_OK)
       {
-        rc_ = setInput(h, in, src, count, on_device, what);
+        rc_ = h->setInput(in, src, count, on_device, what);
       }
     };
     set(h->Fx, Fx, S * n * n, "Fx");
@@ -485,7 +351,7 @@ extern "C"
     {
       return rc_;
     }
-    RC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->have_derivatives = true;
     return NMPC_HIP_OK;
   }
@@ -505,30 +371,24 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[Riccati] limits_per_step must be 0 or 1");
     }
-    RC_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
     const size_t m = h->m, S = h->B * h->T;
     const size_t lim = limits_per_step ? S * m : m;
-    int rc_ = setInput(h, h->U, U, S * m, on_device, "U");
+    int rc_ = h->setInput(h->U, U, S * m, on_device, "U");
     if(rc_ == NMPC_HIP_OK)
     {
-      rc_ = setInput(h, h->lower, lower, lim, on_device, "lower");
+      rc_ = h->setInput(h->lower, lower, lim, on_device, "lower");
     }
     if(rc_ == NMPC_HIP_OK)
     {
-      rc_ = setInput(h, h->upper, upper, lim, on_device, "upper");
+      rc_ = h->setInput(h->upper, upper, lim, on_device, "upper");
     }
     if(rc_ != NMPC_HIP_OK)
     {
       return rc_;
     }
-    RC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     h->limits_per_step = limits_per_step;
     h->have_inputs = true;
     return NMPC_HIP_OK;
@@ -540,24 +400,18 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    RC_TRY(hipSetDevice(h->device));
-    {
-      const int rc_ = waitForOtherStream(h);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
-    int rc_ = setInput(h, h->lam, lambda, h->B, on_device, "lambda");
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    NMPC_CAPI_CHECK(h->waitForOtherStream());
+    int rc_ = h->setInput(h->lam, lambda, h->B, on_device, "lambda");
     if(rc_ == NMPC_HIP_OK)
     {
-      rc_ = setInput(h, h->dlam, dlambda, h->B, on_device, "dlambda");
+      rc_ = h->setInput(h->dlam, dlambda, h->B, on_device, "dlambda");
     }
     if(rc_ != NMPC_HIP_OK)
     {
       return rc_;
     }
-    RC_TRY(hipStreamSynchronize(h->stream));
+    NMPC_CAPI_TRY(hipStreamSynchronize(h->stream));
     return NMPC_HIP_OK;
   }
 
@@ -567,24 +421,16 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    RC_TRY(hipSetDevice(h->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-    if(h->last_stream && h->last_stream != s)
-    {
-      RC_TRY(hipStreamSynchronize(h->last_stream)); // the previous solve writes the buffers this one writes
-    }
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    hipStream_t s = h->streamFor(stream);
+    NMPC_CAPI_CHECK(h->waitBeforeLaunchOn(s)); // the previous solve writes the buffers this one writes
     return launchSolve(h, s);
   }
 
   int nmpc_hip_riccati_solve(nmpc_hip_riccati_handle h)
   {
-    const int rc_ = nmpc_hip_riccati_solve_device(h, nullptr);
-    if(rc_ != NMPC_HIP_OK)
-    {
-      return rc_;
-    }
-    RC_TRY(hipStreamSynchronize(h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(nmpc_hip_riccati_solve_device(h, nullptr));
+    return h->syncLast();
   }
 
   int nmpc_hip_riccati_synchronize(nmpc_hip_riccati_handle h)
@@ -593,9 +439,8 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
     }
-    RC_TRY(hipSetDevice(h->device));
-    RC_TRY(hipStreamSynchronize(h->last_stream ? h->last_stream : h->stream));
-    return NMPC_HIP_OK;
+    NMPC_CAPI_TRY(hipSetDevice(h->device));
+    return h->syncLast();
   }
 
   int nmpc_hip_riccati_field_bytes(nmpc_hip_riccati_handle h, int field, size_t * bytes)
@@ -609,38 +454,9 @@ extern "C"
 
   int nmpc_hip_riccati_get(nmpc_hip_riccati_handle h, int field, void * out, size_t bytes, int on_device)
   {
-    if(!h)
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL handle");
-    }
     size_t want = 0;
-    {
-      const int rc_ = fieldBytes(h, field, &want);
-      if(rc_ != NMPC_HIP_OK)
-      {
-        return rc_;
-      }
-    }
-    if(bytes != want || (!out && want > 0))
-    {
-      return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "[Riccati] get: bytes must equal nmpc_hip_riccati_field_bytes (" + std::to_string(want)
-                                                     + "), got " + std::to_string(bytes));
-    }
-    if(!h->solved)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[Riccati] get needs a solve first");
-    }
-    RC_TRY(hipSetDevice(h->device));
-    hipStream_t s = h->last_stream;
-    if(want > 0)
-    {
-      RC_TRY(hipMemcpyAsync(out, fieldPtr(h, field), want, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    }
-    if(!on_device)
-    {
-      RC_TRY(hipStreamSynchronize(s));
-    }
-    return NMPC_HIP_OK;
+    NMPC_CAPI_CHECK(capi::beginGet<Family>(h, field, out, bytes, &want, fieldBytes, solved, "get needs a solve"));
+    return h->copyOut(out, fieldPtr(h, field), want, on_device, capi::kWaitForHostOnly);
   }
 
   int nmpc_hip_riccati_kernel_name(nmpc_hip_riccati_handle h, const char ** name)
@@ -659,18 +475,11 @@ extern "C"
     {
       return fail(NMPC_HIP_ERR_INVALID_ARGUMENT, "NULL argument");
     }
-    if(!h->timed)
-    {
-      return fail(NMPC_HIP_ERR_NOT_SOLVED, "[Riccati] last_ms needs a solve first");
-    }
-    RC_TRY(hipSetDevice(h->device));
-    RC_TRY(hipEventSynchronize(h->ev1));
-    RC_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
-    return NMPC_HIP_OK;
+    return h->lastMs(ms, "last_ms needs a solve");
   }
 
   const char * nmpc_hip_riccati_last_error(void)
   {
-    return g_riccati_last_error.c_str();
+    return capi::lastError<Family>().c_str();
   }
 }
