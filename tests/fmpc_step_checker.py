@@ -1,6 +1,7 @@
 """ctypes wrapper of the FMPC step CPU checker (tests/cpp/fmpc_step_checker.cpp, g++ -O2 -ffp-contract=off, built into a directory
 the caller owns, never into the tree), and the cases both FMPC step test files run: linearisations of the pinned oracle's models,
-seeded synthetic linearisations, the zero-pivot case and the exactly converged case.
+seeded synthetic linearisations (the shapes at which a run-time offset or mask of the kernel can slip, time-varying dimensions with
+NaN beyond them), the zero-pivot case and the exactly converged case; and the linearised KKT system as equations (kkt_residuals).
 
 Arrays are numpy [B, T, rows, cols] with the capacities (n, m, g) as block sizes, as nmpc_amd.fmpc_step.FmpcStepBatch.step takes them.
 The bar of every comparison of device outputs with the checker is TOL * (1 + |ref|) with TOL = 1e-9; the bars against
@@ -171,16 +172,34 @@ def assert_close(a, b, rtol, atol, what):
 
 # ---- synthetic cases -------------------------------------------------------------------------------------------------------
 # (n, m, g): the smallest shape, one with no input, one that fills no tile with g not a multiple of the MFMA's 4, the largest
-SYNTHETIC_SHAPES = ((1, 1, 1), (2, 0, 1), (3, 2, 5), (16, 16, 32))
+BASE_SHAPES = ((1, 1, 1), (2, 0, 1), (3, 2, 5), (16, 16, 32))
+# where a run-time offset or mask can slip: n, m at 4 / 5, 8 / 9, 12 / 13 and 15 / 16 (a contraction group of four just full or just
+# started), g at 16 / 17 (the second inequality tile empty, or holding one row), 20, 24 and 31 (partly filled), strongly non-square
+BOUNDARY_SHAPES = ((4, 4, 4), (5, 3, 16), (5, 3, 17), (8, 9, 20), (13, 12, 31), (16, 1, 24), (1, 16, 9), (15, 15, 15), (9, 16, 32),
+                   (16, 16, 17))
+SYNTHETIC_SHAPES = BASE_SHAPES + BOUNDARY_SHAPES
+NO_INEQ_SHAPES = ((5, 3, 0), (16, 16, 0))  # g = 0: no inequality tile in the layout; needs update_barrier_eps = 0
+ONE_STEP_SHAPES = ((1, 1, 1), (5, 3, 17), (13, 12, 31))  # run with T = 1: no next record to request
 SYNTHETIC_T = 4
 SYNTHETIC_B = 5
-VARYING_DIMS = ([2, 0, 1, 2], [5, 0, 3, 5])  # m_i and g_i of the (3, 2, 5) case with time-varying dimensions
+VARYING_DIMS = ((2, 0, 1, 2), (5, 0, 3, 5))  # m_i and g_i of the (3, 2, 5) case with time-varying dimensions
+# a two-tile handle (gt() = 2) with T = 5: (m_i, g_i) with the second tile full, dead, absent, holding one row and dead again; with
+# the second tile holding one row, full and dead in turn; and with the second tile dead at every step
+VARYING_SHAPE = (7, 6, 29)
+VARYING_T = 5
+VARYING_CASES = (((6, 0, 3, 6, 1), (29, 16, 0, 17, 5)), ((1, 2, 3, 4, 5), (17, 29, 1, 15, 28)), ((6,) * 5, (16,) * 5))
+
+
+def varying_id(dims) -> str:
+    return "m%s-g%s" % ("".join("%x" % d for d in dims[0]), ".".join(str(d) for d in dims[1]))
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic_case(n: int, m: int, g: int, B: int = SYNTHETIC_B, T: int = SYNTHETIC_T, varying: bool = False, seed: int = 0) -> Case:
+def synthetic_case(n: int, m: int, g: int, B: int = SYNTHETIC_B, T: int = SYNTHETIC_T, varying=False, seed: int = 0) -> Case:
     """Seeded strictly feasible linearisations with Lxx = Luu = I (U uniform in +-1): A = I + 0.1 U, B = 0.3 U, C, D = 0.5 U,
-    Lxu = 0.1 U, Lx, Lu = U, g in [-1.5, -0.5], s, nu in [0.5, 2], x, u, lambda = 0.3 N(0, 1), f = x_{i+1} + 0.1 U, dt = 0.1."""
+    Lxu = 0.1 U, Lx, Lu = U, g in [-1.5, -0.5], s, nu in [0.5, 2], x, u, lambda = 0.3 N(0, 1), f = x_{i+1} + 0.1 U, dt = 0.1.
+    varying: False (the capacities at every step), True (VARYING_DIMS, for the (3, 2, 5) case) or a pair of tuples (m_i, g_i) of
+    length T.  The arrays do not depend on it: the entries beyond a step's dimensions are ordinary numbers."""
     rng = np.random.default_rng(10000 * n + 100 * m + g + 7 * seed)
     U = lambda *shape: rng.uniform(-1, 1, shape)
     eye = lambda k, *lead: np.broadcast_to(np.eye(k), lead + (k, k)).copy()
@@ -189,8 +208,120 @@ def synthetic_case(n: int, m: int, g: int, B: int = SYNTHETIC_B, T: int = SYNTHE
     lin = dict(A=eye(n, B, T) + 0.1 * U(B, T, n, n), B=0.3 * U(B, T, n, m), C=0.5 * U(B, T, g, n), D=0.5 * U(B, T, g, m), Lx=U(B, T, n),
                Lu=U(B, T, m), Lxx=eye(n, B, T), Luu=eye(m, B, T), Lxu=0.1 * U(B, T, n, m), f=var["x"][:, 1:] + 0.1 * U(B, T, n),
                g=rng.uniform(-1.5, -0.5, (B, T, g)), Lx_T=U(B, n), Lxx_T=eye(n, B), current_x=var["x"][:, 0] + 0.1 * U(B, n))
-    md, gd = VARYING_DIMS if varying else (None, None)
-    return Case("synthetic-%dx%dx%d%s" % (n, m, g, "-varying" if varying else ""), n, m, g, T, 0.1, lin, var, None, md, gd)
+    md, gd = (None, None) if varying is False else (VARYING_DIMS if varying is True else varying)
+    if md is not None:
+        assert len(md) == T == len(gd) and 0 <= min(md) and max(md) <= m and 0 <= min(gd) and max(gd) <= g, (md, gd)
+    name = "synthetic-%dx%dx%d%s%s" % (n, m, g, "" if T == SYNTHETIC_T else "-T%d" % T,
+                                       "" if varying is False else "-varying" if varying is True else "-" + varying_id(varying))
+    return Case(name, n, m, g, T, 0.1, lin, var, None, md, gd)
+
+
+def step_dims(case: Case):
+    """(m_i, g_i) of every step, the capacities written out where the case has none."""
+    md = [case.m] * case.T if case.mdims is None else [int(d) for d in case.mdims]
+    gd = [case.g] * case.T if case.gdims is None else [int(d) for d in case.gdims]
+    return md, gd
+
+
+def poisoned(case: Case, variable: bool = False) -> Case:
+    """A copy of `case` with NaN in every entry beyond a step's dimensions, which the boundary promises not to read: the columns
+    >= m_i of B, D and Lxu, the rows and columns >= m_i of Luu, Lu[m_i:], the rows >= g_i of C and D, g[g_i:]; with `variable` also
+    u[m_i:], s[g_i:] and nu[g_i:], which the boundary promises to leave alone."""
+    lin = {k: case.lin[k].copy() for k in ("B", "C", "D", "Lu", "Luu", "Lxu", "g")}
+    var = {k: case.var[k].copy() for k in ("u", "s", "nu")}
+    for i, (mi, gi) in enumerate(zip(*step_dims(case))):
+        for k in ("B", "D", "Lxu", "Luu"):
+            lin[k][:, i, :, mi:] = np.nan
+        lin["Luu"][:, i, mi:, :] = np.nan
+        lin["Lu"][:, i, mi:] = np.nan
+        lin["C"][:, i, gi:, :] = np.nan
+        lin["D"][:, i, gi:, :] = np.nan
+        lin["g"][:, i, gi:] = np.nan
+        var["u"][:, i, mi:] = np.nan
+        var["s"][:, i, gi:] = np.nan
+        var["nu"][:, i, gi:] = np.nan
+    c = case.replace(lin=lin, var=var if variable else None)
+    c.name = case.name + (" poisoned with its variable" if variable else " poisoned")
+    return c
+
+
+def beyond_dims(case: Case):
+    """Boolean masks [T, m] and [T, g]: the entries of u (du, k) and of s, nu (ds, dnu) beyond a step's dimensions."""
+    md, gd = step_dims(case)
+    return (np.arange(case.m)[None, :] >= np.array(md)[:, None], np.arange(case.g)[None, :] >= np.array(gd)[:, None])
+
+
+def assert_poison_left_no_trace(clean, dirty, case: Case, variable: bool, fields=REAL_FIELDS + ("status",)):
+    """`dirty` (the Result on poisoned(case, variable)) has the bits of `clean` (the Result on `case`); where the variable was
+    poisoned too, those entries come back as NaN and every other entry of the variable has the bits of `clean`."""
+    mu, mg = beyond_dims(case)
+    for f in fields:
+        a, b = np.asarray(getattr(clean, f)), np.asarray(getattr(dirty, f))
+        if variable and f in ("u", "vs", "vnu"):
+            mask = np.broadcast_to(mu if f == "u" else mg, b.shape)
+            assert np.isnan(b[mask]).all(), f
+            a, b = np.where(mask, 0.0, a), np.where(mask, 0.0, b)
+        assert a.shape == b.shape and np.array_equal(a, b, equal_nan=True), (case.name, f)
+        if not (variable and f in ("u", "vs", "vnu")):
+            assert not np.isnan(b).any(), (case.name, f)
+
+
+def assert_zero_beyond_dims(r, case: Case):
+    """k, K, du, ds, dnu beyond a step's dimensions are exactly 0."""
+    mu, mg = beyond_dims(case)
+    for f, mask in (("k", mu), ("du", mu), ("ds", mg), ("dnu", mg)):
+        a = np.asarray(getattr(r, f))
+        assert (a[np.broadcast_to(mask, a.shape)] == 0).all(), (case.name, f)
+    K = np.asarray(r.K)  # [B, T, m, n]
+    assert (K[np.broadcast_to(mu[None, :, :, None], K.shape)] == 0).all(), (case.name, "K")
+
+
+# ---- the linearised KKT system, stated as equations ------------------------------------------------------------------------
+def kkt_residuals(case: Case, r) -> dict:
+    """Scaled residuals, per block, of the linear system FmpcSolver::procOnce solves for the delta (FmpcSolver.hpp, the equations
+    behind the Riccati recursion (2.33)-(2.36) and behind (2.27)), evaluated in numpy longdouble from the arrays of `case` (its
+    variable is the one the delta was computed at: r comes from step(case, apply_update=0)), r.barrier_eps and r's delta:
+
+      dynamics        dx_0 = current_x - x_0;   dx_{i+1} = A_i dx_i + B_i du_i + (f_i - x_{i+1})
+      stationarity x  (-lam_i + dt Lx_i + A_i' lam_{i+1} + C_i' nu_i) + dt Lxx_i dx_i + dt Lxu_i du_i + A_i' dlam_{i+1} - dlam_i
+                      + C_i' dnu_i = 0;   (Lx_T - lam_T) + Lxx_T dx_T - dlam_T = 0
+      stationarity u  (dt Lu_i + B_i' lam_{i+1} + D_i' nu_i) + dt Lxu_i' dx_i + dt Luu_i du_i + B_i' dlam_{i+1} + D_i' dnu_i = 0
+      inequality      C_i dx_i + D_i du_i + ds_i + (g_i + s_i) = 0
+      complementarity s_i dnu_i + nu_i ds_i + s_i nu_i - barrier_eps = 0     (elementwise)
+
+    Each block's figure is max over instances of max|residual| / (1 + max|term|), with the terms being the summands written above
+    (matrix-vector products as one term each) of that instance."""
+    L = np.longdouble
+    T, dt = case.T, L(case.dt)
+    md, gd = step_dims(case)
+    lin = {k: v.astype(L) for k, v in case.lin.items()}
+    x, u, lam, s, nu = (case.var[k].astype(L) for k in VAR)
+    dx, du, dlam, ds, dnu = (np.asarray(getattr(r, k)).astype(L) for k in ("dx", "du", "dlam", "ds", "dnu"))
+    eps = np.asarray(r.barrier_eps).astype(L)
+    worst = dict(dynamics=0.0, stationarity_x=0.0, stationarity_u=0.0, inequality=0.0, complementarity=0.0)
+
+    def note(block, terms):
+        res = sum(terms)
+        scale = 1 + max([float(np.abs(t).max()) for t in terms if t.size] + [0.0])
+        if res.size:
+            worst[block] = max(worst[block], float(np.abs(res).max()) / scale)
+
+    for b in range(case.B):
+        note("dynamics", [lin["current_x"][b], -x[b, 0], -dx[b, 0]])
+        for i in range(T):
+            m, g = md[i], gd[i]
+            A, Bm, Cm, Dm = lin["A"][b, i], lin["B"][b, i][:, :m], lin["C"][b, i][:g], lin["D"][b, i][:g, :m]
+            Lxx, Luu, Lxu = lin["Lxx"][b, i], lin["Luu"][b, i][:m, :m], lin["Lxu"][b, i][:, :m]
+            dui, si, nui, dsi, dnui = du[b, i, :m], s[b, i, :g], nu[b, i, :g], ds[b, i, :g], dnu[b, i, :g]
+            note("dynamics", [A @ dx[b, i], Bm @ dui, lin["f"][b, i], -x[b, i + 1], -dx[b, i + 1]])
+            note("stationarity_x", [-lam[b, i], dt * lin["Lx"][b, i], A.T @ lam[b, i + 1], Cm.T @ nui, dt * (Lxx @ dx[b, i]),
+                                    dt * (Lxu @ dui), A.T @ dlam[b, i + 1], -dlam[b, i], Cm.T @ dnui])
+            note("stationarity_u", [dt * lin["Lu"][b, i][:m], Bm.T @ lam[b, i + 1], Dm.T @ nui, dt * (Lxu.T @ dx[b, i]), dt * (Luu @ dui),
+                                    Bm.T @ dlam[b, i + 1], Dm.T @ dnui])
+            note("inequality", [Cm @ dx[b, i], Dm @ dui, dsi, lin["g"][b, i][:g], si])
+            note("complementarity", [si * dnui, nui * dsi, si * nui, np.full(g, -eps[b])])
+        note("stationarity_x", [lin["Lx_T"][b], -lam[b, T], lin["Lxx_T"][b] @ dx[b, T], -dlam[b, T]])
+    return worst
 
 
 def zero_pivot_case(B: int = 3, at: int = 1) -> Case:

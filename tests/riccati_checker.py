@@ -1,6 +1,7 @@
 """ctypes wrapper of the Riccati CPU checker (tests/cpp/riccati_checker.cpp, g++ -O2 -ffp-contract=off, built into a directory the
 caller owns, never into the tree), and the cases both Riccati test files run: derivatives of the pinned oracle's models along a
-rollout, seeded synthetic derivatives, and the retry case.
+rollout, seeded synthetic derivatives (the shapes at which a run-time offset or mask of the kernel can slip, time-varying input
+dimensions with NaN beyond them), and the retry cases.
 
 Arrays are numpy [B, T, rows, cols] with the capacities (n, m) as block sizes, as nmpc_amd.riccati.RiccatiBatch.backward takes them.
 The bar of every comparison of real outputs is TOL * (1 + |ref|) with TOL = 1e-9."""
@@ -192,15 +193,30 @@ def model_case(mdl: str, T: int, t0: float, lim, reg: int, B: int = B_CASE) -> C
 
 
 # ---- synthetic cases -------------------------------------------------------------------------------------------------------
-SYNTHETIC_SHAPES = ((1, 0), (1, 1), (16, 16), (3, 2))  # the smallest, the largest, and one that fills no tile
+BASE_SHAPES = ((1, 0), (1, 1), (16, 16), (3, 2))  # the smallest, the largest, and one that fills no tile
+# where a run-time offset or mask can slip: n, m at 4 / 5, 8 / 9, 12 / 13 and 15 / 16 (a contraction group of four just full or just
+# started), and strongly non-square blocks
+BOUNDARY_SHAPES = ((4, 4), (5, 3), (8, 9), (13, 12), (16, 1), (1, 16), (15, 15), (9, 4), (12, 5), (4, 13))
+SYNTHETIC_SHAPES = BASE_SHAPES + BOUNDARY_SHAPES
+ONE_STEP_SHAPES = ((5, 3), (13, 12))  # run with T = 1: no next record to request
 SYNTHETIC_T = 4
 # (n, m, boxed, reg_type); without an input there is no QP
 SYNTHETIC_CASES = tuple((n, m, boxed, reg) for n, m in SYNTHETIC_SHAPES for boxed in (False, True) for reg in (1, 2) if m > 0 or not boxed)
+ONE_STEP_CASES = tuple((n, m, boxed, reg) for n, m in ONE_STEP_SHAPES for boxed in (False, True) for reg in (1, 2))
+# time-varying input dimensions on a (7, 6) handle with T = 5
+VARYING_SHAPE = (7, 6)
+VARYING_T = 5
+VARYING_DIMS = ((6, 0, 3, 6, 1), (1, 2, 3, 4, 5), (0, 6, 0, 6, 0))
+VARYING_CASES = tuple((dims, boxed) for dims in VARYING_DIMS for boxed in (False, True))
+# the model cases with time-varying input dimensions
+VARYING_MODEL_CASES = tuple(c for c in MODEL_CASES if c[0] in ("vertical", "centroidal"))
 
 
 @functools.lru_cache(maxsize=None)
-def synthetic_case(n: int, m: int, boxed: bool = False, reg: int = 1, B: int = B_CASE, T: int = SYNTHETIC_T) -> Case:
-    """Seeded derivatives with Lxx = I and Luu = I: every Quu_F is positive definite at the first lambda."""
+def synthetic_case(n: int, m: int, boxed: bool = False, reg: int = 1, B: int = B_CASE, T: int = SYNTHETIC_T, dims=None) -> Case:
+    """Seeded derivatives with Lxx = I and Luu = I: every Quu_F is positive definite at the first lambda.  dims: None (m at every
+    step) or a tuple of T input dimensions.  The arrays do not depend on it: the entries beyond a step's dimension are ordinary
+    numbers."""
     rng = np.random.default_rng(100 * n + m)
     u = lambda *shape: rng.uniform(-1, 1, shape)
     d = dict(Fx=np.eye(n) + 0.1 * u(B, T, n, n), Fu=0.3 * u(B, T, n, m), Lx=u(B, T, n), Lu=u(B, T, m),
@@ -208,21 +224,98 @@ def synthetic_case(n: int, m: int, boxed: bool = False, reg: int = 1, B: int = B
              Lxu=0.1 * u(B, T, n, m), Vx_T=u(B, n), Vxx_T=np.broadcast_to(np.eye(n), (B, n, n)).copy())
     U = 0.2 * u(B, T, m) if boxed else None
     lim = (np.full(m, -0.4), np.full(m, 0.4)) if boxed else (None, None)
-    return Case("synthetic-%dx%d-%s-reg%d" % (n, m, "box" if boxed else "free", reg), n, m, T, d, None, U, lim[0], lim[1], reg)
+    if dims is not None:
+        assert len(dims) == T and 0 <= min(dims) and max(dims) <= m, dims
+        dims = np.array(dims, dtype=np.int32)
+    name = "synthetic-%dx%d%s%s-%s-reg%d" % (n, m, "" if T == SYNTHETIC_T else "-T%d" % T,
+                                             "" if dims is None else "-m" + "".join("%x" % v for v in dims), "box" if boxed else "free", reg)
+    return Case(name, n, m, T, d, dims, U, lim[0], lim[1], reg)
+
+
+def step_dims(case: Case):
+    """The input dimension of every step, the capacity written out where the case has none."""
+    return [case.m] * case.T if case.dims is None else [int(v) for v in case.dims]
+
+
+def poisoned(case: Case) -> Case:
+    """A copy of `case` with NaN in every entry beyond a step's input dimension, which the boundary promises not to read: the
+    columns >= m_i of Fu and Lxu, the rows and columns >= m_i of Luu, Lu[m_i:], and U[m_i:] of a boxed case."""
+    d = {k: v.copy() for k, v in case.d.items()}
+    U = None if case.U is None else case.U.copy()
+    for i, mi in enumerate(step_dims(case)):
+        for k in ("Fu", "Lxu", "Luu"):
+            d[k][:, i, :, mi:] = np.nan
+        d["Luu"][:, i, mi:, :] = np.nan
+        d["Lu"][:, i, mi:] = np.nan
+        if U is not None:
+            U[:, i, mi:] = np.nan
+    return Case(case.name + " poisoned", case.n, case.m, case.T, d, case.dims, U, None if case.lower is None else case.lower.copy(),
+                None if case.upper is None else case.upper.copy(), case.reg_type, case.expect)
+
+
+def same_bits(a, b, fields=REAL_FIELDS + INT_FIELDS) -> bool:
+    """Every output field of two results has the same shape, type and bits (NaN equal to NaN)."""
+    for f in fields:
+        x, y = np.asarray(getattr(a, f)), np.asarray(getattr(b, f))
+        if x.shape != y.shape or x.dtype != y.dtype or not np.array_equal(x, y, equal_nan=x.dtype.kind == "f"):
+            print("differs:", f)
+            return False
+    return True
+
+
+def assert_zero_beyond_dims(r, case: Case):
+    """k and K beyond a step's input dimension are exactly 0."""
+    for i, mi in enumerate(step_dims(case)):
+        assert not np.asarray(r.k)[:, i, mi:].any() and not np.asarray(r.K)[:, i, mi:, :].any(), (case.name, i)
+
+
+def assert_box_is_active(ref, case: Case):
+    """The premise of a boxed case with m >= 4: at some step the free set is mixed, and over the case the limits clamp some variable
+    and leave some variable free, so that neither branch of the BoxQP goes unused."""
+    dims = np.array(step_dims(case))
+    fm = np.asarray(ref.free_mask).astype(np.int64)
+    full = (1 << dims.astype(np.int64)) - 1  # [T]
+    free = np.array([[bin(int(v)).count("1") for v in row] for row in fm])
+    print("riccati %s: free variables per step %d .. %d of %d" % (case.name, free[:, dims > 0].min(), free[:, dims > 0].max(), dims.max()))
+    assert (fm & ~full[None, :] == 0).all()  # no bit beyond a step's dimension
+    assert ((free > 0) & (free < dims[None, :])).any(), (case.name, "no step has both clamped and free variables")
 
 
 @functools.lru_cache(maxsize=None)
-def retry_case(luu: float = -0.5, B: int = 1, seed: int = 0) -> Case:
-    """n 3, m 2, T 4; Fx = I + 0.05 U, Fu = 0.1 U (U uniform in +-1), Lxx = I, Luu = I except `luu` I at step 1."""
-    n, m, T = 3, 2, 4
+def retry_case(luu: float = -0.5, B: int = 1, seed: int = 0, n: int = 3, m: int = 2, T: int = 4, at: int = 1, row=None, reg: int = 1) -> Case:
+    """Fx = I + 0.05 U, Fu = 0.1 U (U uniform in +-1), Lxx = I, Lxu = 0, Luu = I except at step `at`: there `luu` I (row = None), or
+    I with `luu` at the diagonal entry (row, row).  The defaults: n 3, m 2, T 4, step 1, the whole diagonal."""
     rng = np.random.default_rng(4242 + seed)
     u = lambda *shape: rng.uniform(-1, 1, shape)
     Luu = np.broadcast_to(np.eye(m), (B, T, m, m)).copy()
-    Luu[:, 1] = luu * np.eye(m)
+    if row is None:
+        Luu[:, at] = luu * np.eye(m)
+    else:
+        Luu[:, at, row, row] = luu
     d = dict(Fx=np.eye(n) + 0.05 * u(B, T, n, n), Fu=0.1 * u(B, T, n, m), Lx=u(B, T, n), Lu=u(B, T, m),
              Lxx=np.broadcast_to(np.eye(n), (B, T, n, n)).copy(), Luu=Luu, Lxu=np.zeros((B, T, n, m)), Vx_T=u(B, n),
              Vxx_T=np.broadcast_to(np.eye(n), (B, n, n)).copy())
-    return Case("retry%g" % luu, n, m, T, d)
+    name = "retry%g" % luu if (n, m, T, at, row, reg) == (3, 2, 4, 1, None, 1) else "retry%g-%dx%d-T%d-at%d-row%s-reg%d" % (
+        luu, n, m, T, at, row, reg)
+    return Case(name, n, m, T, d, reg_type=reg)
+
+
+# (n, m, T, at, row): Luu[row, row] = -0.5 at step `at`, B = 3.  With reg_type 1 each fails at lambda_5 = 0.115 and passes at
+# lambda_6 = 1.934 (seven passes); the margin is wide, so rounding cannot move the decision.
+RETRY_CASES = ((13, 12, 4, 3, 11), (13, 12, 4, 0, 11), (13, 12, 4, 1, 5), (5, 16, 4, 3, 15), (16, 1, 4, 0, 0))
+# with reg_type 2 only these are decision-stable (eight passes, lambda_7 = 51.923 on every instance); tests/test_riccati_host_cpu.py
+# guards that with a perturbation premise
+RETRY_CASES_REG2 = ((13, 12, 4, 0, 11), (16, 1, 4, 0, 0))
+RETRY_B = 3
+
+
+def retry_id(c) -> str:
+    return "%dx%d-T%d-at%d-row%d" % c
+
+
+def retry_shape_case(c, reg: int = 1) -> Case:
+    n, m, T, at, row = c
+    return retry_case(-0.5, RETRY_B, 0, n, m, T, at, row, reg)
 
 
 def concat(cases) -> Case:

@@ -194,3 +194,93 @@ def test_checker_statuses_on_the_special_cases(checker):
         assert (r.status == 6).all(), (shape, r.status)
     r = checker.step(fk.synthetic_case(3, 2, 5, varying=True))
     assert (r.status == 6).all()
+
+
+# ---- the premises of the boundary shapes -------------------------------------------------------------------------------------
+def boundary_cases():
+    """(case, config) of every synthetic case the device tests run beyond the four base shapes."""
+    out = [(fk.synthetic_case(*shape), {}) for shape in fk.BOUNDARY_SHAPES]
+    out += [(fk.synthetic_case(*shape), dict(update_barrier_eps=0)) for shape in fk.NO_INEQ_SHAPES]
+    out += [(fk.synthetic_case(*shape, T=1), {}) for shape in fk.ONE_STEP_SHAPES]
+    out += [(fk.synthetic_case(*fk.VARYING_SHAPE, T=fk.VARYING_T, varying=dims), {}) for dims in fk.VARYING_CASES]
+    return out
+
+
+def test_every_boundary_case_takes_a_full_iteration_on_the_checker(checker):
+    """The premise of the device tests: every G is positive definite and every step length is in (0, 1], so every instance ends as
+    ITERATION_CONTINUED and no output is left unwritten."""
+    lo = 1.0
+    for case, config in boundary_cases():
+        r = checker.step(case, **config)
+        assert (r.status == 6).all(), (case.name, r.status)
+        assert np.isfinite(r.K).all() and np.isfinite(r.P).all() and np.isfinite(r.dnu).all()
+        lo = min(lo, float(r.alpha_s_max.min()), float(r.alpha_nu_max.min()))
+        if config:
+            assert (r.barrier_eps == case.eps).all()  # update_barrier_eps = 0 keeps the caller's
+    print("fmpc_step boundary cases: smallest step length %.3f" % lo)
+    assert 0 < lo <= 1
+
+
+# ---- the checker honours "only the leading m_i, g_i rows and columns are read" --------------------------------------------------
+@pytest.mark.parametrize("dims", fk.VARYING_CASES, ids=fk.varying_id)
+def test_checker_does_not_read_or_write_beyond_a_steps_dimensions(checker, dims):
+    """NaN in every entry beyond a step's dimensions (check_nan on) changes no bit of the checker's result, so the reference of the
+    device's poison test honours the contract itself."""
+    case = fk.synthetic_case(*fk.VARYING_SHAPE, T=fk.VARYING_T, varying=dims)
+    clean = checker.step(case)
+    assert (clean.status == 6).all()
+    for variable in (False, True):
+        dirty = checker.step(fk.poisoned(case, variable))
+        fk.assert_poison_left_no_trace(clean, dirty, case, variable)
+    fk.assert_zero_beyond_dims(clean, case)
+    if min(dims[1]) < fk.VARYING_SHAPE[2]:  # the helper poisons something: the premise of the test itself
+        assert np.isnan(fk.poisoned(case).lin["C"]).any() and np.isnan(fk.poisoned(case, True).var["nu"]).any()
+        assert not np.isnan(fk.poisoned(case).var["nu"]).any()
+
+
+# ---- the checker's delta solves the linearised KKT system ------------------------------------------------------------------------
+KKT_CASES = ([(shape, fk.SYNTHETIC_T, False) for shape in fk.BOUNDARY_SHAPES if shape[2] > 5]
+             + [(shape, 1, False) for shape in fk.ONE_STEP_SHAPES if shape[2] > 5] + [(fk.VARYING_SHAPE, fk.VARYING_T, fk.VARYING_CASES[0])])
+KKT_BAR = 100 * 7.7e-16  # 100 times the measured worst figure: see the test's docstring
+
+
+def test_checker_delta_solves_the_linearised_kkt_system(checker):
+    """Where the pinned oracle cannot reach (g > 16, n, m > 4): the checker's (dx, du, dlambda, ds, dnu) put into the linear system
+    it claims to solve, assembled in numpy longdouble from the case's arrays as the equations themselves (fk.kkt_residuals), not as
+    a Riccati recursion.  The figure of a block is max |residual| / (1 + max |term of the block|).
+
+    Measured on the CPU over these cases (x86-64, g++ -O2 -ffp-contract=off): worst block figure 7.69e-16 (stationarity u 7.69e-16,
+    stationarity x 7.25e-16, inequality 2.32e-16, dynamics 2.06e-16, complementarity 1.98e-16), rounded up to 7.7e-16.  The bar is
+    100 times that, 7.7e-14: the margin leaves room for another order of summation, and a wrong offset or mask in the checker moves
+    a residual to the order of the terms themselves, 1e-2 and more."""
+    assert len(KKT_CASES) == 12
+    worst, instances = {}, 0
+    for shape, T, varying in KKT_CASES:
+        case = fk.synthetic_case(*shape, T=T, varying=varying)
+        r = checker.step(case, apply_update=0)
+        assert (r.status == 6).all(), case.name  # no instance is left out
+        instances += case.B
+        res = fk.kkt_residuals(case, r)
+        print("fmpc_step %s KKT residuals: %s" % (case.name, ", ".join("%s %.2e" % kv for kv in res.items())))
+        for k, v in res.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print("fmpc_step KKT residuals, worst per block: %s; bar %.1e" % (", ".join("%s %.2e" % kv for kv in worst.items()), KKT_BAR))
+    assert instances == 12 * fk.SYNTHETIC_B
+    for k, v in worst.items():
+        assert v <= KKT_BAR, (k, v)
+
+
+def test_kkt_residuals_notice_a_wrong_delta(checker):
+    """The residual check has teeth: one entry of the delta moved by 1e-9 relative, or the delta of a neighbouring inequality row
+    swapped in, puts a block over the bar."""
+    case = fk.synthetic_case(13, 12, 31)
+    r = checker.step(case, apply_update=0)
+    dnu = r.dnu.copy()
+    dnu[0, 2, 30] *= 1 + 1e-9
+    r.dnu = dnu
+    assert max(fk.kkt_residuals(case, r).values()) > KKT_BAR
+    r = checker.step(case, apply_update=0)
+    du = r.du.copy()
+    du[1, 3, [10, 11]] = du[1, 3, [11, 10]]
+    r.du = du
+    assert max(fk.kkt_residuals(case, r).values()) > 1e-6

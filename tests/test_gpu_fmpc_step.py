@@ -88,6 +88,52 @@ def test_time_varying_dimensions_match_the_checker_and_pad_with_zeros(checker, c
         assert np.array_equal(got.vnu[:, i, gi:], case.var["nu"][:, i, gi:])
 
 
+@pytest.mark.parametrize("col_major", (False, True), ids=("row_major", "col_major"))
+@pytest.mark.parametrize("shape", fk.NO_INEQ_SHAPES, ids=lambda s: "%dx%dx%d" % s)
+def test_shapes_without_inequalities_match_the_checker(checker, shape, col_major):
+    """g = 0: the equality-constrained LQ problem.  The layout has no inequality tile and no barrier parameter can be derived, so
+    update_barrier_eps is off and the caller's barrier_eps comes back."""
+    case = fk.synthetic_case(*shape)
+    ref = checker.step(case, update_barrier_eps=0)
+    assert (ref.status == 6).all()
+    got = device_step(case, col_major=col_major, update_barrier_eps=0)
+    fk.compare(got, ref, case.name + (" col-major" if col_major else " row-major"))
+    assert (got.alpha_s_max == 1).all() and (got.alpha_nu_max == 1).all() and np.array_equal(got.barrier_eps, case.eps)
+    assert got.ds.shape == (case.B, case.T, 0) and got.vnu.shape == (case.B, case.T, 0)
+
+
+@pytest.mark.parametrize("col_major", (False, True), ids=("row_major", "col_major"))
+@pytest.mark.parametrize("shape", fk.ONE_STEP_SHAPES, ids=lambda s: "%dx%dx%d" % s)
+def test_a_horizon_of_one_step_matches_the_checker(checker, shape, col_major):
+    case = fk.synthetic_case(*shape, T=1)
+    ref = checker.step(case)
+    assert (ref.status == 6).all()
+    got = device_step(case, col_major=col_major)
+    fk.compare(got, ref, case.name + (" col-major" if col_major else " row-major"))
+
+
+@pytest.mark.parametrize("col_major", (False, True), ids=("row_major", "col_major"))
+@pytest.mark.parametrize("dims", fk.VARYING_CASES, ids=fk.varying_id)
+def test_entries_beyond_a_steps_dimensions_are_neither_read_nor_written(checker, dims, col_major):
+    """A two-tile handle, (7, 6, 29), whose steps fill the second inequality tile, leave it partly filled, or leave it dead.  With
+    NaN in every input entry beyond a step's dimensions (check_nan on) the device returns the bits it returns without; with NaN in
+    the variable beyond them too, those entries come back as they went in and everything else has the same bits."""
+    case = fk.synthetic_case(*fk.VARYING_SHAPE, T=fk.VARYING_T, varying=dims)
+    ref = checker.step(case)
+    assert (ref.status == 6).all()
+    label = case.name + (" col-major" if col_major else " row-major")
+    got = device_step(case, col_major=col_major)
+    fk.compare(got, ref, label)
+    fk.assert_zero_beyond_dims(got, case)
+    for variable in (False, True):
+        dirty = device_step(fk.poisoned(case, variable), col_major=col_major)
+        fk.assert_poison_left_no_trace(got, dirty, case, variable)
+    # the variable beyond a step's dimensions is left alone
+    mu, mg = fk.beyond_dims(case)
+    for a, k, mask in ((got.u, "u", mu), (got.vs, "s", mg), (got.vnu, "nu", mg)):
+        assert np.array_equal(a[:, mask], case.var[k][:, mask]), k
+
+
 # ---- model cases -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", fk.MODELS)
 def test_models_match_the_oracle_over_one_and_four_iterations(checker, model):
@@ -223,3 +269,10 @@ def test_misuse_is_refused(checker):
         sb.step(*[case.lin[k] for k in fk.LIN])
     with pytest.raises(ValueError):
         sb.setStepDims(None, [2] * case.T)
+    # dimensions beyond the capacities of a handle that is smaller than the kernel's largest
+    n, m, g = fk.VARYING_SHAPE
+    sb = fmpc_step.FmpcStepBatch(n, m, g, fk.VARYING_T, 2)
+    for md, gd in (([m] * 4 + [m + 1], None), (None, [g, 0, g + 1, 0, 0]), ([-1] + [m] * 4, None), (None, [31] * 5), ([m] * 4, None)):
+        with pytest.raises(ValueError):
+            sb.setStepDims(md, gd)
+    sb.setStepDims([m] * 5, [g] * 5)

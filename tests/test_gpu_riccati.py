@@ -35,13 +35,7 @@ def device_backward(case: rk.Case, col_major=False, solver=None, retry=True, lam
     return r
 
 
-def same_bits(a, b) -> bool:
-    for f in rk.REAL_FIELDS + rk.INT_FIELDS:
-        x, y = np.asarray(getattr(a, f)), np.asarray(getattr(b, f))
-        if x.shape != y.shape or x.dtype != y.dtype or not np.array_equal(x, y, equal_nan=True):
-            print("differs:", f)
-            return False
-    return True
+same_bits = rk.same_bits
 
 
 def pick(r, idx):
@@ -87,6 +81,49 @@ def test_synthetic_case_matches_checker(checker, n, m, boxed, reg, col_major):
     got = device_backward(case, col_major)
     rk.compare(got, ref, case.name + " device vs checker")
     assert (got.status == 1).all() and (got.n_backward == 1).all() and (got.fail_step == -1).all()
+    if boxed and m >= 4:
+        rk.assert_box_is_active(ref, case)
+
+
+@pytest.mark.parametrize("col_major", [False, True], ids=["row_major", "col_major"])
+@pytest.mark.parametrize("n,m,boxed,reg", rk.ONE_STEP_CASES, ids=lambda v: str(v))
+def test_a_horizon_of_one_step_matches_checker(checker, n, m, boxed, reg, col_major):
+    case = rk.synthetic_case(n, m, boxed, reg, T=1)
+    ref = checker.backward(case)
+    got = device_backward(case, col_major)
+    rk.compare(got, ref, case.name + " device vs checker")
+    assert (got.status == 1).all() and (got.n_backward == 1).all() and (got.fail_step == -1).all()
+    if boxed and m >= 4:
+        rk.assert_box_is_active(ref, case)
+
+
+# ---- entries beyond a step's input dimension -------------------------------------------------------------------------------------
+def assert_poison_leaves_no_trace(checker, case, col_major):
+    """The device on `case` matches the checker, writes exact zeros beyond a step's input dimension, and returns the same bits with
+    NaN in every input entry beyond it."""
+    ref = checker.backward(case)
+    got = device_backward(case, col_major)
+    rk.compare(got, ref, case.name + " device vs checker")
+    assert (got.status == 1).all() and (got.fail_step == -1).all()
+    rk.assert_zero_beyond_dims(got, case)
+    dirty = rk.poisoned(case)
+    assert np.isnan(dirty.d["Fu"]).any() and np.isnan(dirty.d["Luu"]).any()
+    assert same_bits(device_backward(dirty, col_major), got)
+    assert not any(np.isnan(np.asarray(getattr(got, f), dtype=np.float64)).any() for f in rk.REAL_FIELDS)
+
+
+@pytest.mark.parametrize("col_major", [False, True], ids=["row_major", "col_major"])
+@pytest.mark.parametrize("reg", (1, 2))
+@pytest.mark.parametrize("dims,boxed", rk.VARYING_CASES, ids=lambda v: "".join(map(str, v)) if isinstance(v, tuple) else ("box" if v else "free"))
+def test_entries_beyond_a_steps_input_dimension_are_not_read(checker, dims, boxed, reg, col_major):
+    """A (7, 6) handle whose steps have every input dimension from 0 to 6; the blocks beyond them hold ordinary numbers, then NaN."""
+    assert_poison_leaves_no_trace(checker, rk.synthetic_case(*rk.VARYING_SHAPE, boxed, reg, T=rk.VARYING_T, dims=dims), col_major)
+
+
+@pytest.mark.parametrize("c", rk.VARYING_MODEL_CASES, ids=rk.model_case_id)
+def test_entries_beyond_a_models_input_dimension_are_not_read(checker, c):
+    """The model cases with time-varying input dimension, whose padding is zeros in test_model_case_matches_checker_and_oracle."""
+    assert_poison_leaves_no_trace(checker, rk.model_case(*c), False)
 
 
 # ---- the retry loop --------------------------------------------------------------------------------------------------------------
@@ -101,6 +138,22 @@ def test_retry_case(checker):
     again = device_backward(case, lam=got.lam, dlam=got.dlam)
     assert again.status[0] == 1 and again.n_backward[0] == 1 and again.lam[0] == got.lam[0]
     assert np.array_equal(again.k, got.k) and np.array_equal(again.K, got.K)
+
+
+@pytest.mark.parametrize("c,reg", [(c, 1) for c in rk.RETRY_CASES] + [(c, 2) for c in rk.RETRY_CASES_REG2],
+                         ids=lambda v: rk.retry_id(v) if isinstance(v, tuple) else "reg%d" % v)
+def test_retry_at_other_shapes_steps_and_rows(checker, c, reg):
+    """Luu[row, row] = -0.5 at step `at`, the first or the last step the sweep meets or one in between, on full-size blocks: seven
+    passes to lambda_6 = 1.934 with reg_type 1, eight to lambda_7 = 51.923 with reg_type 2."""
+    case = rk.retry_shape_case(c, reg)
+    ref = checker.backward(case)
+    got = device_backward(case)
+    rk.compare(got, ref, case.name + " device vs checker")
+    passes, lam = (7, 1.9342813) if reg == 1 else (8, 51.923)
+    assert (ref.status == 1).all() and (ref.n_backward == passes).all() and (ref.fail_step == c[3]).all()
+    assert (np.abs(ref.lam - lam) < (1e-7 if reg == 1 else 1e-3)).all()
+    assert (got.status == 1).all() and (got.n_backward == passes).all() and (got.fail_step == c[3]).all()
+    assert np.array_equal(got.lam, ref.lam) and np.array_equal(got.dlam, ref.dlam)
 
 
 def test_retry_gives_up_at_lambda_max(checker):
@@ -210,3 +263,10 @@ def test_misuse_codes():
         assert L.nmpc_hip_riccati_get(h, riccati.FIELD_K_FB, vp(buf), nb.value, 0) == _capi.OK and buf.any()
     finally:
         assert L.nmpc_hip_riccati_destroy(h) == _capi.OK
+    # input dimensions beyond the capacity of a handle that is smaller than the kernel's largest
+    n, m = rk.VARYING_SHAPE
+    s = riccati.RiccatiBatch(n, m, rk.VARYING_T, 2)
+    for dims in ([m, m, m + 1, m, m], [m, -1, m, m, m], [16] * 5, [m] * 4):
+        with pytest.raises(ValueError):
+            s.setInputDims(dims)
+    s.setInputDims([m] * 5)

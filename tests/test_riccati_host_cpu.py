@@ -165,25 +165,63 @@ def numpy_backward(case: rk.Case, b: int, lam0=1e-4, dlam0=1.0, retry=True, cfg=
     return r
 
 
-@pytest.mark.parametrize("n,m,boxed,reg", rk.SYNTHETIC_CASES, ids=lambda v: str(v))
-def test_checker_matches_numpy_on_synthetic_derivatives(checker, n, m, boxed, reg):
-    case = rk.synthetic_case(n, m, boxed, reg)
+def assert_checker_matches_numpy(checker, case):
+    """The checker on `case` against the NumPy restatement, which is handed the leading m_i columns and rows alone."""
     got = checker.backward(case)
     assert (got.status == 1).all() and (got.n_backward == 1).all() and (got.fail_step == -1).all()
     worst = 0.0
     for b in range(case.B):
         ref = numpy_backward(case, b)
         assert ref["status"] == 1 and ref["n_backward"] == 1
-        for i in range(case.T):
-            worst = max(worst, rk.rel_err(got.k[b, i], ref["k"][i]), rk.rel_err(got.K[b, i], ref["K"][i]))
-            if boxed:
+        for i, mi in enumerate(rk.step_dims(case)):
+            worst = max(worst, rk.rel_err(got.k[b, i, :mi], ref["k"][i]), rk.rel_err(got.K[b, i, :mi], ref["K"][i]))
+            if case.constrained and mi > 0:
                 assert got.qp_retval[b, i] == ref["qp_retval"][i]
                 assert int(got.free_mask[b, i]) == sum(1 << j for j in ref["qp_free"][i])
         worst = max(worst, rk.rel_err(got.dV[b], ref["dV"]))
     print("riccati %s checker vs numpy: %.2e" % (case.name, worst))
     assert worst <= rk.TOL
-    if boxed:
-        assert (got.free_mask != (1 << m) - 1).any()  # the limits bind somewhere
+    if case.constrained:
+        assert (got.free_mask != (1 << case.m) - 1).any()  # the limits bind somewhere
+        if case.m >= 4:
+            rk.assert_box_is_active(got, case)
+    return got
+
+
+@pytest.mark.parametrize("n,m,boxed,reg", rk.SYNTHETIC_CASES, ids=lambda v: str(v))
+def test_checker_matches_numpy_on_synthetic_derivatives(checker, n, m, boxed, reg):
+    assert_checker_matches_numpy(checker, rk.synthetic_case(n, m, boxed, reg))
+
+
+@pytest.mark.parametrize("n,m,boxed,reg", rk.ONE_STEP_CASES, ids=lambda v: str(v))
+def test_checker_matches_numpy_on_a_horizon_of_one_step(checker, n, m, boxed, reg):
+    assert_checker_matches_numpy(checker, rk.synthetic_case(n, m, boxed, reg, T=1))
+
+
+# ---- the checker honours "only the leading m_i columns and rows of a block are read" ---------------------------------------------
+@pytest.mark.parametrize("reg", (1, 2))
+@pytest.mark.parametrize("dims,boxed", rk.VARYING_CASES, ids=lambda v: "".join(map(str, v)) if isinstance(v, tuple) else ("box" if v else "free"))
+def test_checker_does_not_read_beyond_a_steps_input_dimension(checker, dims, boxed, reg):
+    """NaN in every entry beyond a step's input dimension changes no bit of the checker's result, and the result is the NumPy
+    restatement's on the leading blocks."""
+    case = rk.synthetic_case(*rk.VARYING_SHAPE, boxed, reg, T=rk.VARYING_T, dims=dims)
+    clean = assert_checker_matches_numpy(checker, case)
+    dirty_case = rk.poisoned(case)
+    assert np.isnan(dirty_case.d["Luu"]).any() and (not boxed or np.isnan(dirty_case.U).any())  # the helper poisons something
+    assert rk.same_bits(clean, checker.backward(dirty_case))
+    rk.assert_zero_beyond_dims(clean, case)
+    assert not any(np.isnan(np.asarray(getattr(clean, f), dtype=np.float64)).any() for f in rk.REAL_FIELDS)
+
+
+@pytest.mark.parametrize("c", rk.VARYING_MODEL_CASES, ids=rk.model_case_id)
+def test_checker_does_not_read_beyond_a_models_input_dimension(checker, c):
+    case = rk.model_case(*c)
+    assert len(set(rk.step_dims(case))) > 1
+    clean = checker.backward(case)
+    assert (clean.status == 1).all()
+    dirty_case = rk.poisoned(case)
+    assert np.isnan(dirty_case.d["Fu"]).any()
+    assert rk.same_bits(clean, checker.backward(dirty_case))
 
 
 # ---- the retry case ----------------------------------------------------------------------------------------------------------
@@ -199,6 +237,42 @@ def test_retry_case_succeeds_at_the_seventh_pass(checker):
         assert rk.rel_err(got.k[0, i], ref["k"][i]) <= rk.TOL and rk.rel_err(got.K[0, i], ref["K"][i]) <= rk.TOL
     once = checker.backward(case, retry=False)
     assert once.status[0] == -2 and once.n_backward[0] == 1 and once.fail_step[0] == 1 and once.lam[0] == 1e-4
+
+
+@pytest.mark.parametrize("c", rk.RETRY_CASES, ids=rk.retry_id)
+def test_retry_at_other_shapes_steps_and_rows_succeeds_at_the_seventh_pass(checker, c):
+    """One negative diagonal entry of Luu, -0.5, at step `at`: as the (3, 2) case, lambda_5 = 0.115 fails and lambda_6 = 1.934 passes,
+    and the failing step is reported whether it is the first the sweep meets (at = T - 1) or the last (at = 0)."""
+    case = rk.retry_shape_case(c)
+    assert case.B == 3 and case.d["Luu"][0, c[3], c[4], c[4]] == -0.5 and np.trace(case.d["Luu"][0, c[3]]) == c[1] - 1.5
+    got = checker.backward(case)
+    assert (got.status == 1).all() and (got.n_backward == 7).all() and (got.fail_step == c[3]).all()
+    assert (np.abs(got.lam - 1.9342813) < 1e-7).all() and (np.abs(got.dlam - 16.777216) < 1e-12).all()
+    for b in range(case.B):
+        ref = numpy_backward(case, b)
+        assert ref["n_backward"] == 7 and got.lam[b] == ref["lam"]
+        for i in range(case.T):
+            assert rk.rel_err(got.k[b, i], ref["k"][i]) <= rk.TOL and rk.rel_err(got.K[b, i], ref["K"][i]) <= rk.TOL
+
+
+@pytest.mark.parametrize("c", rk.RETRY_CASES_REG2, ids=rk.retry_id)
+def test_retry_with_reg_type_2_is_decision_stable_where_the_device_runs_it(checker, c):
+    """reg_type 2 (lambda on Vxx): eight passes, lambda_7 = 51.923, on every instance; and the premise of the device test, that
+    rounding cannot move a decision: the integers are the same with Fx perturbed by 1e-12 relative."""
+    case = rk.retry_shape_case(c, reg=2)
+    got = checker.backward(case)
+    assert (got.status == 1).all() and (got.n_backward == 8).all() and (got.fail_step == c[3]).all()
+    assert (np.abs(got.lam - 51.923) < 1e-3).all()
+    rng = np.random.default_rng(77)
+    for trial in range(4):
+        d = {k: v.copy() for k, v in case.d.items()}
+        d["Fx"] = d["Fx"] * (1 + 1e-12 * rng.uniform(-1, 1, d["Fx"].shape))
+        assert not np.array_equal(d["Fx"], case.d["Fx"])
+        moved = checker.backward(rk.Case(case.name + " perturbed", case.n, case.m, case.T, d, reg_type=2))
+        for f in ("status", "n_backward", "fail_step"):
+            assert np.array_equal(getattr(moved, f), getattr(got, f)), f
+        assert np.array_equal(moved.lam, got.lam) and np.array_equal(moved.dlam, got.dlam)
+        assert rk.rel_err(moved.K, got.K) <= rk.TOL  # and the answer moves with the perturbation, not with a decision
 
 
 def test_retry_case_gives_up_after_twelve_passes(checker):
