@@ -152,6 +152,14 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
   {
     return p ? v : 0.0;
   }
+  /** fmin() of values that are results of arithmetic — never signalling NaNs —: the one v_min_f64, which returns the other operand
+      for a quiet NaN.  (fmin() itself quiets both operands first, an instruction each, because it cannot know.) */
+  NMPC_D static double minQuiet(double a, double b_)
+  {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b_));
+    return r;
+  }
 
   /** Derivatives of timestep i of instance `inst_l` (this lane's instance in the LINEARISATION mapping) -> record. */
   struct PointQ
@@ -159,18 +167,20 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
     double x[N], u;
     double lo, hi; //!< input limits of the timestep (box-constrained solves)
   };
-  NMPC_D static void loadPointQ(int i, const double * px, const double * pu, PointQ & p)
+  /** (x_i, u_i) of one (instance, timestep) pair: `ox`, `ou` are the pair's byte offsets from the tile bases of X and U (uniform), so a
+      load is base + 32-bit offset + immediate, as Base::ld everywhere else. */
+  NMPC_D void loadPointQ(unsigned ox, unsigned ou, PointQ & p) const
   {
 #pragma unroll
     for(int j = 0; j < N; j++)
     {
-      p.x[j] = px[(static_cast<size_t>(i) * N + j) * LW];
+      p.x[j] = Base::ld(Base::Xt + j * LW, ox);
     }
-    p.u = pu[static_cast<size_t>(i) * LW];
+    p.u = Base::ld(Base::Ut, ou);
   }
   /** One record entry.  kFull = false: entries the compiler knows to be constants (the literal zeros and ones of the
       model's Jacobians and Hessians, the padding beyond n) are not written again — the record already holds them from
-      the pass's first (full) chunk.  An LDS store costs a lone wave 14 cycles, 25 when the four waves of the workgroup
+      layRecordConstants() (kFull = true, once per launch).  An LDS store costs a lone wave 14 cycles, 25 when the four waves of the workgroup
       write (scripts/ubench_issue_cost.hip): the 49 stores of a record were most of the linearisation's time. */
   template<bool kFull>
   NMPC_D static void put(double * at, double v)
@@ -232,6 +242,22 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
     put<kFull>(rec + oZero, 0.0);
     return recipFast(fabs(u[0]) + 1.0);
   }
+  /** The constant entries of this wave's 64 records (the literal zeros and ones of the model's derivatives, the padding beyond n, the
+      zero slot), once per launch: every wave of the workgroup calls it ahead of the first pass, behind ingestInputs(), which stages the
+      caller's rows in the chunk.  The chunk is wave-private and nothing else writes the records, so the passes' linearisations
+      (lineariseStep<false>) leave these entries alone; the entries that depend on the point are written here too, from an arbitrary
+      one, and again by every chunk of every pass before they are read. */
+  NMPC_D void layRecordConstants() const
+  {
+    PointQ p;
+#pragma unroll
+    for(int j = 0; j < N; j++)
+    {
+      p.x[j] = 0.0;
+    }
+    p.u = p.lo = p.hi = 0.0;
+    lineariseStep<true>(0, 0.0, p, chunk + static_cast<size_t>(wl) * kRecQ + (wl / 16) * kInstPad);
+  }
 
   /** One backward pass (DDPSolver::backwardPass, DDPSolver.hpp:342-534) of the four instances of this wave.  Entered by
       all four waves after the master's post(kCmdBackward); inputs and results go through the LDS mailboxes. */
@@ -248,8 +274,11 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
     const int sel_l = static_cast<int>(mailIn(inst_l, 2));
     const double t0_l = mailIn(inst_l, 3);
     const int lane_l = static_cast<int>(lane - lane % kQuadInstances) + inst_l;
-    const double * px = Base::Xt + static_cast<size_t>(sel_l) * (Base::rowsX() * LW) + lane_l;
-    const double * pu = Base::Ut + static_cast<size_t>(sel_l) * (Base::rowsU() * LW) + lane_l;
+    // byte offsets of the instance's column in the current half of X and U, and in the single-copy arrays of the gains
+    constexpr unsigned kRowB = static_cast<unsigned>(LW * sizeof(double)); // one row of a tile
+    const unsigned x_l = (static_cast<unsigned>(sel_l) * static_cast<unsigned>(Base::rowsX() * LW) + static_cast<unsigned>(lane_l)) * 8u;
+    const unsigned u_l = (static_cast<unsigned>(sel_l) * static_cast<unsigned>(Base::rowsU() * LW) + static_cast<unsigned>(lane_l)) * 8u;
+    const unsigned g_l = static_cast<unsigned>(lane_l) * 8u;
     double * rec_l = chunk + static_cast<size_t>(wl) * kRecQ + (wl / 16) * kInstPad;
     double * gains = chunk + 64 * kRecQ + 4 * kInstPad;
     const double * gain_l = gains + static_cast<size_t>(wl) * kGainRec; // linearisation mapping: read at the chunk boundary
@@ -297,6 +326,10 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
     };
 
     // ---- terminal value function    DDPSolver.hpp:349-352
+    // The lane with ts_l = 0 evaluates them and hands them to the 16 lanes of the instance's block through the instance's share of
+    // the gain staging area: free here (the last pass's gains went out before its closing barrier, this pass's first gain is
+    // stored behind the reads below; LDS is in order within a wave).  The derivative records are not touched: their constant
+    // entries are laid once per launch (layRecordConstants()).
     if(ts_l == 0)
     {
       StateDimVector xT, vx;
@@ -304,25 +337,28 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
 #pragma unroll
       for(int j = 0; j < N; j++)
       {
-        xT[j] = px[(static_cast<size_t>(T) * N + j) * LW];
+        xT[j] = Base::ld(Base::Xt + (static_cast<size_t>(T) * N + j) * LW, x_l);
       }
       lin_problem.calcTerminalCostDeriv(t0_l + T * lin_problem.dt(), xT, vx, vxx);
+      double * park_l = gains + static_cast<size_t>(wl) * kGainRec;
 #pragma unroll
       for(int r = 0; r < 4; r++)
       {
 #pragma unroll
         for(int c = 0; c < 4; c++)
         {
-          rec_l[4 * r + c] = (r < N && c < N) ? vxx(r < N ? r : 0, c < N ? c : 0) : 0.0;
+          park_l[4 * r + c] = (r < N && c < N) ? vxx(r < N ? r : 0, c < N ? c : 0) : 0.0;
         }
-        rec_l[16 + r] = (r < N) ? vx[r < N ? r : 0] : 0.0;
+        park_l[16 + r] = (r < N) ? vx[r < N ? r : 0] : 0.0;
       }
     }
-    double Vxx = rec_q[aE];
-    double VxM = pick(c1, rec_q[16 + row]); // Vx in column 1, zero elsewhere
+    const double * park_q = gains + static_cast<size_t>(blk * 16) * kGainRec;
+    double Vxx = park_q[aE];
+    double VxM = pick(c1, park_q[16 + row]); // Vx in column 1, zero elsewhere
 
     double dV0_l = 0, dV1_l = 0;
     bool ok = true;
+    double quu_min = 0; // smallest pivot of the unguarded chunk under way
     double k_next = 0;
     bool have_next = false;
     const size_t tile_T = static_cast<size_t>(T);
@@ -334,7 +370,8 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
     {
       constexpr int kReg = decltype(reg_tag)::value; // Configuration::reg_type, a compile-time constant in here
       // guarded: the reference's semantics for a pass that fails at this timestep or has failed before (nothing is
-      // accumulated or saved from then on); unguarded: the caller looks at `ok` when the chunk is done and repeats it
+      // accumulated or saved from then on); unguarded: the caller looks at the chunk's smallest pivot (`quu_min`) when the
+      // chunk is done and repeats it
       constexpr bool kGuarded = decltype(guarded_tag)::value;
       loadOperands(ts_next, o_next);
       // ---- Q terms    DDPSolver.hpp:386-408   (mma(X, Y, C) = X^T Y + C)
@@ -348,7 +385,7 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       const double Quu = quadBroadcast<0>(Wq);
       const double Qu = quadBroadcast<1>(Wq);
       const double Qr = quadBroadcast<0>(S); // Qux[row]
-      const double Qxr = quadBroadcast<1>(S); // Qx[row]
+      // (Qx[row] is S itself in the lanes of column 1, the only ones the update of VxM below is kept from: no broadcast)
 
       // ---- regularisation    :421-441
       double Quu_F = Quu, QAr = QA, Qrr = Qr;
@@ -391,7 +428,19 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       }
       else
       {
-        step_ok = !(Quu_F <= 0);
+        if constexpr(kGuarded)
+        {
+          step_ok = !(Quu_F <= 0);
+        }
+        else
+        {
+          // the chunk's pass-failure test, once behind the chunk: some pivot fails !(Quu_F <= 0) exactly if the smallest one does.
+          // A NaN pivot passes that test; the minimum returns its other operand for a NaN (as fmin() does: fmin(inf, NaN) = inf,
+          // fmin(-1, NaN) = -1 on the host), so the running minimum, which starts at +inf, never is one and passes a NaN over as
+          // well.  +-0.0 fail either way.  A compare and a scalar AND per timestep become one v_min_f64.
+          quu_min = minQuiet(quu_min, Quu_F);
+          step_ok = true;
+        }
         inv = (!kGuarded || step_ok) ? recipFast(Quu_F) : 0.0;
         k = -1 * (Qu * inv);
       }
@@ -412,7 +461,7 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       const double VnT = fma(QA, Kr, fma(Kc, Qr, fma(KQc, Kr, QxxT)));
       Vxx = 0.5 * (Vn + VnT);
       // Qx + K^T Quu k + K^T Qu + Qux^T k
-      VxM = pick(c1, fma(Qr, k, fma(Kr, Qu, fma(KQr, k, Qxr))));
+      VxM = pick(c1, fma(Qr, k, fma(Kr, Qu, fma(KQr, k, S))));
 
       // ---- save gains    :529-530 (staged, see flushGains)
       if constexpr(kGuarded)
@@ -428,10 +477,6 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       have_next = true;
     };
 
-    /** Gains of the chunk starting at timestep i_first: LDS -> k_list_ / K_list_ in HBM, by the lane of each (instance,
-        timestep) pair in the linearisation mapping, which also takes the running max of |k_i| / (|u_i| + 1)
-        (DDPSolver.hpp:217-221; uinv = this lane's 1 / (|u_i| + 1) from the chunk's linearisation): two instructions per
-        chunk here instead of an LDS read and two instructions per timestep in the recursion. */
     const int b_l = b - static_cast<int>(lane) + lane_l; // global index of this lane's instance in the linearisation mapping
     auto loadLimits = [&](int i, PointQ & p)
     {
@@ -442,42 +487,55 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
       }
     };
     double krn_l = 0;
-    auto flushGains = [&](int i_first, double uinv)
+    // This lane's timestep in the chunk with the terminal step — the only chunk in which it can lie beyond the horizon — and the byte
+    // offsets of that (instance, timestep) pair: of (x, u) in the current half, of k and K.  They step back by a chunk's rows with every
+    // request / flush, so the chunk boundary has no index arithmetic of its own.
+    const int n_chunks = (T + kChunkSteps - 1) / kChunkSteps;
+    const int i_tail = (n_chunks - 1) * kChunkSteps + ts_l;
+    const bool tail_in_T = i_tail < T;
+    unsigned ox = x_l + static_cast<unsigned>(i_tail) * (N * kRowB), ou = u_l + static_cast<unsigned>(i_tail) * kRowB;
+    unsigned ok_g = g_l + static_cast<unsigned>(i_tail) * kRowB, oK_g = g_l + static_cast<unsigned>(i_tail) * (N * kRowB);
+    /** Gains of the staged chunk, the youngest not yet flushed: LDS -> k_list_ / K_list_ in HBM, by the lane of each (instance,
+        timestep) pair in the linearisation mapping, which also takes the running max of |k_i| / (|u_i| + 1)
+        (DDPSolver.hpp:217-221; uinv = this lane's 1 / (|u_i| + 1) from the chunk's linearisation): two instructions per
+        chunk here instead of an LDS read and two instructions per timestep in the recursion.
+        \param tail the staged chunk is the one with the terminal step */
+    auto flushGains = [&](bool tail, double uinv)
     {
-      const int i = i_first + ts_l;
-      const double flag = (i < T) ? gain_l[gLive] : 0.0;
+      const double flag = (tail && !tail_in_T) ? 0.0 : gain_l[gLive];
       bool save = flag != 0.0;
       if constexpr(kConstrained)
       {
         const int code = static_cast<int>(flag);
         if(save)
         {
-          Base::tileBase(buf.qp_ret, tile_T)[static_cast<size_t>(i) * LW + lane_l] = (code >> 2) - 8;
-          Base::tileBase(buf.qp_free, tile_T)[static_cast<size_t>(i) * LW + lane_l] = static_cast<unsigned>((code >> 1) & 1);
+          // (rows of 64 four-byte entries: half the byte offset of k's row)
+          *reinterpret_cast<int *>(reinterpret_cast<char *>(Base::tileBase(buf.qp_ret, tile_T)) + (ok_g >> 1)) = (code >> 2) - 8;
+          *reinterpret_cast<unsigned *>(reinterpret_cast<char *>(Base::tileBase(buf.qp_free, tile_T)) + (ok_g >> 1)) =
+              static_cast<unsigned>((code >> 1) & 1);
         }
         save = (code & 1) != 0;
       }
       if(save)
       {
         const double kv = gain_l[gK];
-        Base::kt[static_cast<size_t>(i) * LW + lane_l] = kv;
+        Base::st(Base::kt, ok_g, kv);
 #pragma unroll
         for(int c = 0; c < N; c++)
         {
-          Base::Kt[(static_cast<size_t>(i) * N + c) * LW + lane_l] = gain_l[gKfb + c];
+          Base::st(Base::Kt + c * LW, oK_g, gain_l[gKfb + c]);
         }
         krn_l = fmax(krn_l, fabs(kv) * uinv);
       }
+      ok_g -= kChunkSteps * kRowB;
+      oK_g -= kChunkSteps * N * kRowB;
     };
     auto runChunks = [&](auto reg_tag)
     {
-      const int n_chunks = (T + kChunkSteps - 1) / kChunkSteps;
       PointQ pt;
-      {
-        const int i = ((n_chunks - 1) * kChunkSteps + ts_l < T) ? (n_chunks - 1) * kChunkSteps + ts_l : T - 1;
-        loadPointQ(i, px, pu, pt);
-        loadLimits(i, pt);
-      }
+      int i_pt = tail_in_T ? i_tail : T - 1; // timestep of the point in `pt`
+      loadPointQ(x_l + static_cast<unsigned>(i_pt) * (N * kRowB), u_l + static_cast<unsigned>(i_pt) * kRowB, pt);
+      loadLimits(i_pt, pt);
       double uinv_prev = 0; // 1 / (|u| + 1) of this lane's timestep in the chunk whose gains are staged
       for(int ch = n_chunks - 1; ch >= 0; ch--)
       {
@@ -487,9 +545,8 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
 #ifdef NMPC_AMD_PROFILE_2W
           const unsigned long long tl = __builtin_readcyclecounter();
 #endif
-          const int i = (i0 + ts_l < T) ? i0 + ts_l : T - 1;
-          // (the terminal blocks above were parked in the records of the lanes with ts_l = 0: the first chunk rewrites all)
-          uinv_now = (ch == n_chunks - 1) ? lineariseStep<true>(i, t0_l, pt, rec_l) : lineariseStep<false>(i, t0_l, pt, rec_l);
+          const int i = i_pt;
+          uinv_now = lineariseStep<false>(i, t0_l, pt, rec_l); // (the constant entries: layRecordConstants(), once per launch)
 #ifdef NMPC_AMD_PROFILE_2W
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifndef NMPC_AMD_PROFILE_QP
@@ -502,14 +559,16 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
         // go out, then the next chunk's (x, u) are requested — both have the 16 recursion steps below to complete
         if(ch + 1 < n_chunks)
         {
-          flushGains(i0 + kChunkSteps, uinv_prev);
+          flushGains(ch + 2 == n_chunks, uinv_prev);
         }
         uinv_prev = uinv_now;
-        if(!Pair::kNominalTail || ch > 0) // (kNominalTail: the last chunk keeps its own (x, u) for the nominal records below)
+        if(ch > 0) // (the last chunk keeps its own (x, u): kNominalTail writes the nominal records from them below)
         {
-          const int in = i0 - kChunkSteps + ts_l; // (unconditional, clamped: the last request is never used)
-          loadPointQ(in > 0 ? in : 0, px, pu, pt);
-          loadLimits(in > 0 ? in : 0, pt);
+          ox -= kChunkSteps * N * kRowB;
+          ou -= kChunkSteps * kRowB;
+          i_pt = i0 - kChunkSteps + ts_l;
+          loadPointQ(ox, ou, pt);
+          loadLimits(i_pt, pt);
         }
         const int hi = (i0 + kChunkSteps - 1 < T) ? i0 + kChunkSteps - 1 : T - 1;
 #ifdef NMPC_AMD_QUAD_NO_STRAIGHT
@@ -533,6 +592,7 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
             // +0.8 %).  Measured and not kept: 12 timesteps (bipedal, T = 300) as straight-line code are 2.4 % SLOWER than
             // the guarded loop — code that runs once per pass is fetched cold, the loop's is resident.
             const double Vxx_s = Vxx, VxM_s = VxM, dV0_s = dV0_l, dV1_s = dV1_l;
+            quu_min = __builtin_inf();
             auto straight = [&](auto r_tag)
             {
               constexpr int R = decltype(r_tag)::value;
@@ -552,7 +612,7 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
             {
               straight(std::integral_constant<int, 4>());
             }
-            if(__all(ok))
+            if(__all(!(quu_min <= 0))) // (ok was true in every lane on the way in)
             {
               *live_q = need ? 1.0 : 0.0; // the 16 lanes of a block: the flags of the chunk's 16 timesteps
               continue;
@@ -578,7 +638,7 @@ struct QuadSolver : PairSolver<Problem, kConstrained, true, (kConstrained || kFa
           step(reg_tag, std::true_type(), i, i - i0, oa, 0, ob);
         }
       }
-      flushGains(0, uinv_prev);
+      flushGains(n_chunks == 1, uinv_prev);
       // The forward pass that follows starts from timestep 0 and takes its nominal (x, u, k, K) from LDS records that a prefetching
       // wave keeps ahead of it; its first groups used to be a round trip to HBM behind the pass barrier, for values that are HERE:
       // (x, u) of timesteps 0 .. 15 in the linearisation lanes' registers, the gains in the staging area.  Lane (instance, timestep)
@@ -881,6 +941,7 @@ __global__ __launch_bounds__(kQuadWaves * 64) void ddp_solve_quad_kernel(const P
       fullBarrier();
     }
   }
+  solver.layRecordConstants(); // (resumable launches too: LDS does not outlive a launch)
   if(threadIdx.x / 64 == 0)
   {
     if constexpr(kResumable)
